@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- Act3D keypose training step (BASELINE.json configs[1]) on N MI355X GPUs of one node.
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5                  the headline step only: set up, warm up, time, print
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full           + every other leg (sequential step, hot path only, kernel
+                                                                  rooflines, `secondary` workloads, CPU baseline)
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs D what the last timed step computed, as D/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 One step = zero_grad + forward (frozen synthetic CLIP-RN50-shaped backbone, FPN, coarse-to-fine ghost-point
 attention) + loss + backward + fused AdamW (+ gradient all-reduce over RCCL for N > 1), on a synthetic batch of the
 18-PerAct-task shapes: 4 cameras 256x256, 3 ghost-point levels, 1000 ghost points, E=60.  Prints ONE JSON line.
-`value` = keyframe samples/s over all ranks; inputs are resident in HBM before the timed region.
+`value` = keyframe samples/s over all ranks; inputs are resident in HBM before the timed region.  Inputs, initial weights
+and the device sampler are seeded: the same arguments give the same inputs in every run.  The backward kernels accumulate
+with atomics and AdamW's first steps are sign-like, so two runs of ONE build drift apart step by step: after 25 steps the
+dumped parameters of two such runs differed by 4e-3 of their norm and the loss by 13 % (9.10 vs 7.89), after 105 steps the
+loss by 0.5 %; the first step's loss is bit-identical.  Compare builds against that spread.
 """
 import argparse
 import importlib
@@ -27,7 +34,7 @@ sys.path.insert(0, ROOT)
 # timed step still executes one backbone pass, one FPN / hot-path forward + backward and one AdamW step; the backbone pass it executes
 # belongs to the batch the next step consumes (the maps the first timed step reads come from the last warm-up step, the maps the last
 # timed step writes are read after the timed region: K timed steps = K backbone passes + K of everything else).  The line also
-# carries `sequential_step`: the same K steps with the backbone inside its own step (A3D_PREFETCH_BACKBONE=0 makes that the headline).
+# carries `sequential_step` under --full: the same K steps with the backbone inside its own step (A3D_PREFETCH_BACKBONE=0 makes that the headline).
 PREFETCH_BACKBONE = os.environ.get("A3D_PREFETCH_BACKBONE", "1") == "1"
 PERACT_BOUNDS = np.array([[-0.1101, -0.5558, 0.7129], [0.6481, 0.5184, 1.5116]])
 
@@ -64,6 +71,46 @@ def build_model(a3d, device, backbone_dtype, levels=3, ghost_points=1000):
     m.fpn_dtype = backbone_dtype
     m.train()
     return m
+
+
+MIOPEN_DB = os.path.join(ROOT, "profiles", "miopen_db")
+
+
+def prepare_convolution_search():
+    """Keeps MIOpen's find mode (torch.backends.cudnn.benchmark) from dominating the set-up.  The frozen backbone / FPN run 16
+    convolution problems through MIOpen; searched from nothing, find mode spent 90 s on them at the first forward / backward:
+      * it compiles and times the naive direct solvers (ConvDirectNaiveConv{Fwd,Bwd,Wrw}: reference implementations, 140 - 1900 ms
+        per call where the chosen implicit-GEMM solvers take 0.02 - 0.45 ms).  They are never picked; they are excluded;
+      * it searches the kernel instance of every tunable solver.  profiles/miopen_db/ holds the user find database and user
+        performance database one such search wrote (solver ranking and kernel instance per problem; names carry the MIOpen version,
+        another version ignores them and searches).  MIOpen gets a temporary copy as its user database directory, so it neither
+        writes into the tree nor depends on the home directory.
+    The solvers picked are the ones the full search picks.  Anything already set in the environment wins."""
+    for d in ("FWD", "BWD", "WRW"):
+        os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_" + d, "0")
+    if "MIOPEN_USER_DB_PATH" not in os.environ and os.path.isdir(MIOPEN_DB):
+        import atexit
+        import shutil
+        import tempfile
+        tmp = tempfile.mkdtemp(prefix="a3d_miopen_db_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        for f in os.listdir(MIOPEN_DB):
+            shutil.copy(os.path.join(MIOPEN_DB, f), tmp)
+        os.environ["MIOPEN_USER_DB_PATH"] = tmp
+
+
+DUMP_MAX_ELEMS = 4 << 20          # per array: 16 MiB of float32, the whole dump stays far under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """Writes what a caller of the timed step holds after its last call as path/<name>.npy (float32).  An array longer than
+    DUMP_MAX_ELEMS is stored as a fixed sample: the elements at seeded, sorted positions (the same positions in every run)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(a3d, B_cpu, steps):
@@ -527,11 +574,18 @@ def main():
                          "(main_keypose.py:49) x ~4 keyframes per episode (<= 5, datasets/dataset_engine.py chunking)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--backbone-dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline step also run every other leg: the sequential (no prefetch) step, the hot path alone, "
+                         "the kernel rooflines, the `secondary` workloads (diffusion training / sampling, joint step, fp8 attention; "
+                         "the joint step under data parallelism for --gpus N) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32): its loss and "
+                         "the flat parameter buffer after its AdamW update")
+    ap.add_argument("--skip-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--kernels-only", action="store_true",
                     help="only the dominant-kernel micro-benchmarks (used for the rocprofv3 --pmc passes)")
     ap.add_argument("--skip-secondary", action="store_true",
-                    help="skip the ChainedDiffuser entries (diffusion training step, 100-step sampling) of `secondary`")
+                    help="with --full: skip the ChainedDiffuser entries (diffusion training step, 100-step sampling) of `secondary`")
     ap.add_argument("--only-cfg5", action="store_true", help="run only the configs[4] / fp8-attention secondary entry and print it")
     ap.add_argument("--cpu-batch", type=int, default=2)
     ap.add_argument("--cpu-steps", type=int, default=5)
@@ -546,6 +600,7 @@ def main():
         dist.init_process_group(backend="nccl", init_method="env://")
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
+    prepare_convolution_search()
     if os.environ.get("A3D_CUDNN_BENCHMARK", "1") == "1":
         torch.backends.cudnn.benchmark = True        # MIOpen find mode for the frozen backbone / FPN convolutions
     a3d = importlib.import_module("act3d-chained-diffuser_amd")
@@ -612,12 +667,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "parameters": flat.flat})
 
     was_graphed = graphed is not None
     joint_dp = None
-    if world > 1 and not args.skip_secondary and os.environ.get("A3D_BENCH_JOINT_DP", "1") == "1":
+    if args.full and world > 1 and not args.skip_secondary and os.environ.get("A3D_BENCH_JOINT_DP", "1") == "1":
         # BASELINE configs[3] under data parallelism: every rank takes part (collectives), rank 0 reports it in `secondary`
-        # (A3D_BENCH_JOINT_DP=0 or --skip-secondary leave the run at the headline step only)
+        # (--full only; A3D_BENCH_JOINT_DP=0 or --skip-secondary leave it out)
         del graphed
         torch.cuda.empty_cache()
         try:
@@ -648,6 +705,7 @@ def main():
         }
         if graph_err:
             res["config"]["graph_capture_error"] = graph_err
+    if rank == 0 and args.full:
         if was_graphed and PREFETCH_BACKBONE and world == 1 and not args.skip_secondary:
             # the same step without the cross-step overlap: backbone -> FPN -> hot path -> backward -> AdamW strictly in order
             try:
@@ -744,6 +802,7 @@ def main():
                 res["cpu_baseline"] = cpu_baseline(a3d, args.cpu_batch, args.cpu_steps)
             except Exception as e:
                 res["cpu_baseline"] = {"error": repr(e)[:300]}
+    if rank == 0:
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

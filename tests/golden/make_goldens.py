@@ -110,6 +110,8 @@ def golden_blocks():
         y, _ = lay(seq1=s1, seq1_key_padding_mask=mask, seq2=s2, seq2_key_padding_mask=None, seq1_pos=pe(x1),
                    seq2_pos=pe(x2), seq1_sem_pos=sem, seq2_sem_pos=None, ada_sgnl=ada)
     out["parallel_attention_layer"] = dict(seed=41, s1=s1, s2=s2, x1=x1, x2=x2, ada=ada, mask=mask, out=y)
+    # two files, each under the size limit for a committed file (tests/test_oracle_golden.py merges them)
+    save("blocks_mha.pt", {k: out.pop(k) for k in ("mha_self_mask", "mha_cross_plain")})
     save("blocks.pt", out)
 
 

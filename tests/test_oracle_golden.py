@@ -20,6 +20,8 @@ G = os.path.join(HERE, "golden")
 
 
 def load(name):
+    if name == "blocks.pt":      # stored as two files, each under the size limit for a committed file
+        return {**torch.load(os.path.join(G, name), weights_only=False), **torch.load(os.path.join(G, "blocks_mha.pt"), weights_only=False)}
     return torch.load(os.path.join(G, name), weights_only=False)
 
 
