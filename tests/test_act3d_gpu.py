@@ -121,14 +121,26 @@ def _check_golden_grads(r, cfg, m, fmaps):
 @pytest.mark.parametrize("tag", ACT3D_TAGS)
 def test_act3d_vs_reference_golden(a3d, dev, tag):
     """Ghost points injected from the reference's record.  The two *_128_* tags are BASELINE.json configs[0]:
-    batch 1, one 128x128 camera, one ghost-point level (1000 points in training, 10000 at evaluation)."""
+    batch 1, one 128x128 camera, one ghost-point level (1000 points in training, 10000 at evaluation).
+
+    Every tag's forward comparison runs twice: with autograd recording (the parameters require gradients, so the eval tags too take
+    the both-parts-P attention forward) and once more under torch.no_grad() (the adaptive-P forward that evaluation and ghost-point
+    sampling run in production), against the same record at the same tolerances."""
     r, cfg, names = _act3d_case(tag)
     P = act3d_params(cfg, r["seed"], r["gain"], names)
     m = build_model(a3d, dev, cfg, P, cfg["Ng"], cfg["train"], **r.get("model_kw", {}))
     inp, fmaps, feats = _golden_inputs(r, cfg, dev)
-    out = m(None, inp["pcd"].to(dev), inp["instr"].to(dev), inp["curr_gripper"].to(dev),
-            gt_action=inp["action"].to(dev) if cfg["train"] else None,
-            ghost_points=[g.to(dev) for g in r["ghost"]], visual_features=feats)
+
+    def fwd():
+        return m(None, inp["pcd"].to(dev), inp["instr"].to(dev), inp["curr_gripper"].to(dev),
+                 gt_action=inp["action"].to(dev) if cfg["train"] else None,
+                 ghost_points=[g.to(dev) for g in r["ghost"]], visual_features=feats)
+
+    with torch.no_grad():
+        out_ng = fwd()
+    _check_golden_forward(tag + " (no_grad)", r, cfg, out_ng, inp["pcd"])
+    del out_ng
+    out = fwd()
     _check_golden_forward(tag, r, cfg, out, inp["pcd"])
     if not cfg["train"]:
         return

@@ -248,6 +248,13 @@ def test_attn_block_fwd_bwd(a3d, dev, B, Lq, S, E, H, rope, masked, mode):
     report_grad(a3d, "attn_block d out_b", mha.out_proj.bias.grad, cob.grad, gtol * sc, 2e-3)
     report_grad(a3d, "attn_block d ln_g", norm.weight.grad, cg.grad, gtol * sc, 2e-3)
     report_grad(a3d, "attn_block d ln_b", norm.bias.grad, cb.grad, gtol * sc, 2e-3)
+    # the gradient-free route through the same call site (need_bwd False -> nograd: the adaptive-P forward of attention16.hip,
+    # the single-query forward for Lq = 1), same oracle, same tolerance
+    with torch.no_grad():
+        y_ng = O.attn_block(dq.detach(), dk.detach(), dv.detach(), dr.detach(), None if q_xyz is None else q_xyz.to(dev),
+                            None if k_xyz is None else k_xyz.to(dev), None if kmask is None else kmask.to(dev), mha, norm, H)
+    assert not y_ng.requires_grad
+    report(f"attn_block[{mode}] fwd (no_grad)", y_ng, ref, 1e-4)
 
 
 @pytest.mark.parametrize("B,S,rope", [(3, 200, False), (70, 130, True), (64, 4097, True)])
