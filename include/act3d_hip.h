@@ -82,7 +82,11 @@ int a3d_proj_rope_split(const float* X, int ldx, const float* W, int ldw, const 
                         float scale0, void* rows0, int rows0_width, void* planes0, const float* xyz1, float scale1,
                         void* rows1, int rows1_width, void* planes1, const float* freq, int B, int N, int Npad, int E,
                         int H, void* stream);
-/* dY[:, :E] = scale * R(xyz)^T * sum_s dR[s];  dR: [nsplit][B][H][Npad][16] fp32 (grad w.r.t. rotated rows). */
+/* dY[:, :E] = scale * R(xyz)^T * sum_s dR[s];  dR: [nsplit][B][H][Npad][16] fp32 (grad w.r.t. rotated rows).  Rows n >= N of dR are not
+ * read; neither is channel 15, except by the opt-in row-per-thread kernel (A3D_ROPE_MERGE_ROWS=1), which loads whole 16-float records
+ * and discards it.  Columns E .. ldy of dY are not written.  A3D_ROPE_MERGE_ROWS=1 / A3D_ROPE_MERGE_PAIRS=1 (read once per process)
+ * select two measured-and-kept alternatives of the kernel for E = 60 / 120; all three are held to the same float64 bound by
+ * tests/test_rope_operands_gpu.py. */
 int a3d_rope_merge_bwd(const float* dR, int nsplit, const float* xyz, const float* freq, float scale, float* dY,
                        int ldy, int B, int N, int Npad, int E, int H, void* stream);
 
@@ -136,7 +140,11 @@ int a3d_dropout_mask(unsigned char* out, size_t n, const unsigned long long* dro
  * channel 15 of the hi part of the ROWS -- REQUIRED for the value rows of a3d_attn16_fwd_rows).
  * q must carry log2(e) (pass scale * log2 e to the *_split16 writers; a3d_rope_merge_bwd takes the same scale): scores and
  * LSE2 are in log2 units.  drop_state NULL or drop_p == 0: no dropout; otherwise Philox keep flags as a3d_attn_fwd_dropout.
- * Sp <= 16384. */
+ * Sp <= 16384.
+ * Pad convention of the two writers below (pinned by tests/test_rope_operands_gpu.py): rows n >= N are zero in channels 0-14 of every
+ * part and channel 15 of the lo part is zero everywhere; with parts | 8 (rows) / parts | 4 (hi plane) channel 15 of the hi part is
+ * exactly 1.0 on EVERY row below Npad, padded rows included (the attention kernels mask keys >= S by position, so the padded ones
+ * are never weighted), and 0 otherwise.  Rows and planes written by one call carry identical bits. */
 int a3d_rope_split16(const float* Y, int ldy, const float* xyz, const float* freq, float scale, void* rows_out,
                      void* planes_out, int plane_parts, int B, int N, int Npad, int E, int H, void* stream);
 int a3d_proj_rope_split16(const float* X, int ldx, const float* W, int ldw, const float* bias, int K, const float* xyz0,

@@ -5,7 +5,7 @@ tests/test_attn16_core_gpu.py (the kernels against them).  Nothing here imports 
 
 Conventions (pinned by the known-answer case of the CPU file and again on the device):
   * operands are rows16 tensors [B][H][Npad][32] fp16, hi(16) | lo(16) of the 16-padded head row (head dim 15); value rows carry
-    1.0 in channel 15 of the hi part; padded rows are zero.  The value an operand CARRIES is hi + lo, exact in float64: the
+    1.0 in channel 15 of the hi part of every row below Npad; padded rows are zero otherwise.  The value an operand CARRIES is hi + lo, exact in float64: the
     reference is computed from carried values, so operand rounding is not part of the error under test.
   * scores are in log2 units: s2 = q . k (q already holds scale * log2 e), w = 2^s2 / sum_k 2^s2, LSE2 = m + log2 sum_k 2^(s2 - m).
   * dQ, dK, dV are the plain derivatives of sum(O * dO) with respect to the carried q, k, v: the ln 2 of d w / d s2 is inside
@@ -89,7 +89,9 @@ def pad_to(n, m):
 
 # ------------------------------------------------------------------------------------------------ operands
 def make_rows16(x, ones=False, npad=None):
-    """[B][H][N][15] float -> rows16 [B][H][Npad][32] fp16 (hi | lo); ones: 1.0 in channel 15 of the hi part of the N real rows."""
+    """[B][H][N][15] float -> rows16 [B][H][Npad][32] fp16 (hi | lo); ones: 1.0 in channel 15 of the hi part of EVERY row below Npad,
+    padded rows included -- the convention of the product's writer (write_operand_formats16 with parts | 8, pinned by
+    tests/test_rope_operands_gpu.py); keys >= S are masked by position in the kernels, so the padded ones are never weighted."""
     B, H, N, d = x.shape
     assert d == HD
     npad = pad_to(N, 64) if npad is None else npad
@@ -100,7 +102,7 @@ def make_rows16(x, ones=False, npad=None):
     rows[:, :, :N, :HD] = hi
     rows[:, :, :N, 16:16 + HD] = lo
     if ones:
-        rows[:, :, :N, HD] = 1.0
+        rows[:, :, :, HD] = 1.0
     return rows
 
 

@@ -83,7 +83,8 @@ def test_operand_builders_carry_what_they_are_given():
     c = R.carried(rows, 37)
     # two roundings to half an fp16 ulp; below 2^-14 fp16 is subnormal (spacing 2^-24), which caps the low part's accuracy
     assert ((c - x).abs() <= 2.0 ** -22 * x.abs() + 2.0 ** -25).all()
-    assert (rows[:, :, :37, 15] == 1).all() and (rows[:, :, 37:] == 0).all() and (rows[:, :, :, 31] == 0).all()
+    # the writers' convention: the 1.0 of the denominator channel sits on every row below Npad, padded rows are zero otherwise
+    assert (rows[:, :, :, 15] == 1).all() and (rows[:, :, 37:, :15] == 0).all() and (rows[:, :, 37:, 16:] == 0).all() and (rows[:, :, :, 31] == 0).all()
     grid = torch.randint(-2048, 2049, (2, 3, 37, 15), generator=g).to(F64) / 64      # on the fp16 grid: carried exactly
     rg = R.make_rows16(grid)
     assert torch.equal(R.carried(rg, 37), grid) and (rg[..., 16:] == 0).all()

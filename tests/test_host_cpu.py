@@ -59,6 +59,60 @@ def test_c_abi_argument_validation_without_gpu():
     assert lib.a3d_linear_wgrad_ws(None, 0, None, 0, None, 0, None, 4, 4, 4, None, 0, None) == -22
 
 
+def test_rope_writer_argument_validation_without_gpu():
+    """The RoPE / projection operand writers and the merge reject bad geometry, alignment and flags on the host, before any launch,
+    with the error code and a3d_last_error_string naming the entry point (tests/test_rope_operands_gpu.py runs the accepted calls)."""
+    a3d = load_pkg()
+    lib = a3d.lib.load()
+    d = ctypes.c_void_p(64)                                                          # 16-byte aligned, never dereferenced
+    odd = ctypes.c_void_p(68)                                                        # 4-byte aligned only
+
+    def refused(name, *args, named=None):
+        assert getattr(lib, name)(*args) == -22, name
+        assert (named or name).encode() in lib.a3d_last_error_string(), (name, lib.a3d_last_error_string())
+
+    ok16 = dict(parts=2, B=1, N=10, Npad=64, E=60, H=4)
+    def split16(**kw):
+        a = dict(ok16, **kw)
+        return (d, 60, None, None, 1.0, d, None, a["parts"], a["B"], a["N"], a["Npad"], a["E"], a["H"], None)
+    refused("a3d_rope_split16", *split16(Npad=96))                                   # Npad % 64
+    refused("a3d_rope_split16", *split16(Npad=0))                                    # Npad < N
+    refused("a3d_rope_split16", *split16(E=61))                                      # E != 15 H
+    refused("a3d_rope_split16", *split16(E=45, H=3))                                 # E % 6
+    refused("a3d_rope_split16", *split16(N=0))
+    for parts in (0, 3, 4, 8, 16 | 2, -1):
+        refused("a3d_rope_split16", *split16(parts=parts))                           # parts & 3 must be 1 or 2, no bits above 8
+        assert b"plane parts" in lib.a3d_last_error_string()
+    refused("a3d_rope_split16", d, 60, None, None, 1.0, None, None, 2, 1, 10, 64, 60, 4, None)       # no output
+    refused("a3d_rope_split16", d, 60, d, None, 1.0, d, None, 2, 1, 10, 64, 60, 4, None)             # xyz without freq
+    refused("a3d_rope_split", d, 60, None, None, 1.0, d, 48, None, 1, 10, 100, 60, 4, None)          # Npad % 64
+    # the two wrappers forward to a3d_rope_split, which is the name the message carries
+    refused("a3d_rope_split_qk", d, 60, None, None, 1.0, d, 1, 10, 64, 60, 5, None, named="a3d_rope_split")      # E != 15 H
+    refused("a3d_split_vt", d, 60, d, 1, 10, 32, 60, 4, None, named="a3d_rope_split")                            # Npad % 64
+
+    def proj16(X=d, ldx=60, K=60, parts0=2, parts1=1, rows1=None, Npad=64, E=60, H=4, rows0=d):
+        return (X, ldx, d, K, None, K, None, 1.0, rows0, None, parts0, None, 1.0, rows1, None, parts1, None, 1, 10, Npad, E, H, None)
+    refused("a3d_proj_rope_split16", *proj16(K=62))                                  # K % 4
+    refused("a3d_proj_rope_split16", *proj16(K=0))
+    refused("a3d_proj_rope_split16", *proj16(ldx=62))                                # ldx % 4
+    refused("a3d_proj_rope_split16", *proj16(X=odd))                                 # X not 16-byte aligned
+    refused("a3d_proj_rope_split16", *proj16(parts0=3))                              # bad parts, block 0
+    refused("a3d_proj_rope_split16", *proj16(rows1=d, parts1=0))                     # bad parts, block 1 (only when it is written)
+    refused("a3d_proj_rope_split16", *proj16(Npad=72))                               # Npad % 64
+    refused("a3d_proj_rope_split16", *proj16(E=61))                                  # E != 15 H
+    refused("a3d_proj_rope_split16", *proj16(E=150, H=10))                           # E > 128
+    refused("a3d_proj_rope_split16", *proj16(rows0=None))                            # block 0 writes nothing
+    refused("a3d_proj_rope_split", odd, 60, d, 60, None, 60, None, 1.0, d, 48, None, None, 1.0, None, 32, None, None, 1, 10, 64, 60, 4, None)
+    refused("a3d_rope_merge_bwd", d, 0, None, None, 1.0, d, 60, 1, 10, 64, 60, 4, None)              # nsplit < 1
+    refused("a3d_rope_merge_bwd", d, 1, None, None, 1.0, d, 60, 1, 10, 64, 61, 4, None)              # E != 15 H
+    refused("a3d_rope_merge_bwd", d, 1, None, None, 1.0, d, 60, 1, 10, 8, 60, 4, None)               # Npad < N
+    refused("a3d_rope_merge_bwd", d, 1, d, None, 1.0, d, 60, 1, 10, 64, 60, 4, None)                 # xyz without freq
+    refused("a3d_rope_merge_bwd", None, 1, None, None, 1.0, d, 60, 1, 10, 64, 60, 4, None)
+    refused("a3d_rope_rows_f32", d, 60, None, None, 1.0, d, 1, 10, 64, 61, 4, None)                  # E != 15 H
+    refused("a3d_rope_rows_f32", d, 30, None, None, 1.0, d, 1, 10, 64, 60, 4, None)                  # ldy < E
+    refused("a3d_rope_rows_f32", d, 60, None, None, 1.0, d, 1, 10, 5, 60, 4, None)                   # Npad < N
+
+
 def test_c_abi_host_side_planning_functions():
     """Workspace / launch planning entry points are pure host code: callable without a GPU, and consistent."""
     a3d = load_pkg()
