@@ -895,7 +895,7 @@ __global__ __launch_bounds__(512) void dn_rest_loop_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------ tail
 __global__ __launch_bounds__(512) void dn_tail_kernel(const float* __restrict__ pos_feats, const float* __restrict__ rot_feats,
                                                       const float* __restrict__ traj, int D, a3d_dn_tail_params p,
-                                                      float* __restrict__ traj_out, int L, int E, int t_step, int warm) {
+                                                      float* __restrict__ traj_out, int L, int E, int row, int terminal, int warm) {
   __shared__ __attribute__((aligned(16))) float Xs[DR * LDX], Ts[DR * LDX], Us[DR * 16];
   const int b = blockIdx.x;
   const int Epad = (E + 15) & ~15;
@@ -917,8 +917,8 @@ __global__ __launch_bounds__(512) void dn_tail_kernel(const float* __restrict__ 
     float mo = Us[r * 16 + c] + (c < 3 ? traj[gi] : 0.f);
     if (p.cond_mask && p.cond_mask[gi]) mo = p.cond_data[gi];
     float out = mo;
-    if (t_step > 0) {
-      const float* cf = ((c < 3) ? p.coef_pos : p.coef_rot) + (size_t)t_step * 3;
+    if (!terminal) {
+      const float* cf = ((c < 3) ? p.coef_pos : p.coef_rot) + (size_t)row * 3;
       const float x0 = fminf(fmaxf(mo, -1.0f), 1.0f);
       out = cf[0] * x0 + cf[1] * traj[gi];
       if (p.noise) out += cf[2] * p.noise[gi];
@@ -978,11 +978,11 @@ __global__ __launch_bounds__(256) void rope_rows_f32_kernel(const float* __restr
 // Synchronisation: agent-scope release / acquire on a ready queue (sample -> streamers) and a per-sample completion counter
 // (streamers -> sample); all workgroups are co-resident (grid <= CU count, one workgroup per CU by LDS size), every spin loop is
 // bounded and raises an abort flag instead of hanging.
-struct DnLayerDev { a3d_dn_cross_params c; a3d_dn_rest_params r; };      // c.mod, r.s_mod, r.f_mod: BASES of the [T][2E] tables
+struct DnLayerDev { a3d_dn_cross_params c; a3d_dn_rest_params r; };      // c.mod, r.s_mod, r.f_mod: BASES of the [rows][2E] tables
 struct DnPersist {
   const DnLayerDev* layers;       // device array [n_traj + n_pos + n_rot]
   a3d_dn_head_params head;
-  a3d_dn_tail_params tail;        // tail.noise: BASE of the [T][B][L][D] step noise (row t is used at step t > 0), or NULL
+  a3d_dn_tail_params tail;        // tail.noise: BASE of the [rows][B][L][D] step noise (unread at the terminal step), or NULL
   float* traj;                    // [B][L][D] in / out
   float* qbuf;                    // [B][16][128] published queries of the sample's current layer
   float* part;                    // Op [nse][B][H][16][16] | Mp [nse][B][H][16]   (nse = nsplit * nsub)
@@ -991,7 +991,12 @@ struct DnPersist {
   float* kvx;                     // [2 roles][B][2][NT * 16][2E] rotated keys | values of the self-attention, exchanged between a
                                   // sample's row tiles (NT > 1 only; two buffers alternate from layer to layer)
   float* xbuf;                    // [U][2][16][128]: x after the trajectory stack (primary -> helper) | rotation features (helper -> primary)
-  int B, L, NT, D, E, H, S, Sp, nsplit, nsub, n_traj, n_pos, n_rot, t_first, nsteps, spin_limit;
+  int B, L, NT, D, E, H, S, Sp, nsplit, nsub, n_traj, n_pos, n_rot, nsteps, spin_limit;
+  // Step `step` of the launch reads row  row_first + row_inc * step  of every per-step table (AdaLN modulation, posterior
+  // coefficients, step noise); the step whose row is term_row is the terminal one (the in-painted network output is the result, no
+  // reverse step).  a3d_dn_persist: tables by timestep, rows t_first, t_first - 1, ..., terminal at row 0 (row_inc -1, term_row 0);
+  // a3d_dn_persist_sched: tables by step position, rows row_first, row_first + 1, ..., term_row = the last row or -1 (none).
+  int row_first, row_inc, term_row;
   long long* prof;                // development aid (A3D_DN_PROF=1): phase timestamps, see a3d_dn_persist_prof; else NULL
 };
 constexpr int DNP_PROF_WORDS = 256;      // long longs: [0, 96) 32 items x {ticket, ready, done} of streamer 0; [96, 96 + 7 * 16) layer marks of sample 0; [250..] head / tail
@@ -1360,7 +1365,7 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
   for (int i = t; i < 4 * DR * LDX; i += blockDim.x) smem[i] = 0.f;          // pads of the four row tiles
   __syncthreads();
   for (int step = 0; step < a.nsteps; ++step) {
-    const int t_step = a.t_first - step;
+    const int row = a.row_first + a.row_inc * step;
     DNP_REFRESH();
     if (role == 0) DNP_MARK(250);
     if (role == 1) {
@@ -1439,7 +1444,7 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
         const a3d_dn_cross_params& c = dnp_args(ap).layers[l].c;
         wg_zero_pad(As, LDX, E, Epad);
         wg_zero_pad(Ts, LDX, E, Epad);
-        wg_adaln(Xs, LDX, c.sem ? c.sem + (size_t)r0 * E : nullptr, c.mod ? c.mod + (size_t)t_step * 2 * E : nullptr, As, LDX, L, E);
+        wg_adaln(Xs, LDX, c.sem ? c.sem + (size_t)r0 * E : nullptr, c.mod ? c.mod + (size_t)row * 2 * E : nullptr, As, LDX, L, E);
         wg_linear<0>(As, LDX, E, c.q_w, E, c.q_b, E, Ts, LDX);
         wg_rope(Ts, LDX, 0, 1, Tr, 16, c.freq, L, E, 1.0f / sqrtf((float)HD));
         DNP_MARK(96 + 7 * l + 1);
@@ -1466,8 +1471,8 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
       // ---- (2) while the streamers work: this layer's vectors -> LDS, weights touched in L2, pads, operation table
       {
         const a3d_dn_rest_params& p = dnp_args(ap).layers[l].r;
-        const float* s_mod = p.s_mod ? p.s_mod + (size_t)t_step * 2 * E : nullptr;
-        const float* f_mod = p.f_mod ? p.f_mod + (size_t)t_step * 2 * E : nullptr;
+        const float* s_mod = p.s_mod ? p.s_mod + (size_t)row * 2 * E : nullptr;
+        const float* f_mod = p.f_mod ? p.f_mod + (size_t)row * 2 * E : nullptr;
         float* const vd[12] = {Ps, Ps + 128, Ps + 256, Ps + 384, Ps + 640, Ps + 1024, Ps + 1152, Ps + 1280, Ps + 1408, Ps + 1664, Ps + 2176,
                                Ps + 2304};
         const VecList vl = {{p.c_out_b, p.c_ln_g, p.c_ln_b, p.s_in_w ? s_mod : nullptr, p.s_in_w ? p.s_in_b : nullptr,
@@ -1611,11 +1616,11 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
         float mo = Us[r * 16 + c] + (c < 3 ? old : 0.f);
         if (p.cond_mask && p.cond_mask[gi]) mo = p.cond_data[gi];
         float out = mo;
-        if (t_step > 0) {
-          const float* cf = ((c < 3) ? p.coef_pos : p.coef_rot) + (size_t)t_step * 3;
+        if (row != a.term_row) {
+          const float* cf = ((c < 3) ? p.coef_pos : p.coef_rot) + (size_t)row * 3;
           const float x0 = fminf(fmaxf(mo, -1.0f), 1.0f);
           out = cf[0] * x0 + cf[1] * old;
-          if (p.noise) out += cf[2] * p.noise[(size_t)t_step * a.B * Lf * D + gi];
+          if (p.noise) out += cf[2] * p.noise[(size_t)row * a.B * Lf * D + gi];
         }
         Tr[r * 16 + c] = out;
         dnp_st(&a.traj[gi], out);                    // the helper workgroup reads the rows next step
@@ -1791,26 +1796,29 @@ extern "C" int a3d_dn_persist_prof(const int* sync, int B, int L, int n_layers, 
   return A3D_OK;
 }
 
-extern "C" int a3d_dn_persist(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot, const a3d_dn_head_params* head,
-                              const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
-                              int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int t_first, int nsteps, void* stream) {
+// Both entry points of the persistent sampler: `name` labels the error strings, rows_ok is the entry's own check of its step
+// arguments, (row_first, row_inc, term_row) is the table addressing of DnPersist.
+static int dnp_launch(const char* name, const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot, const a3d_dn_head_params* head,
+                      const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
+                      int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int row_first, int row_inc, int term_row, int nsteps,
+                      bool rows_ok, const char* row_label, void* stream) {
   int rc = A3D_OK;
   if (B <= 0 || L <= 0 || L > 4 * DR || E <= 0 || E > 128 || (E % 6) != 0 || H * HD != E) {
-    set_error("a3d_dn_persist: bad shape (B=%d L=%d E=%d H=%d; L <= 64, E = 15 H <= 128)", B, L, E, H);
+    set_error("%s: bad shape (B=%d L=%d E=%d H=%d; L <= 64, E = 15 H <= 128)", name, B, L, E, H);
     return A3D_ERR_ARG;
   }
   const int NT = (L + DR - 1) / DR, U = B * NT;
   static_assert(sizeof(a3d_dn_layer_params) == sizeof(DnLayerDev), "layer table layout");
   if (!layers_dev || !head || !tail || !traj || !qbuf || !part || !xbuf || !sync || (NT > 1 && !kvx) || n_traj < 0 || n_pos < 1 || n_rot < 1 || D < 4 ||
-      D > 16 || std::min(L, DR) * D > DN_MISC_XYZ || S <= 0 || Sp < S || (Sp % 64) != 0 || nsplit < 1 || nsplit * dnp_nsub(H) > 16 || H > 8 || nsteps < 1 || t_first < nsteps - 1 ||
+      D > 16 || std::min(L, DR) * D > DN_MISC_XYZ || S <= 0 || Sp < S || (Sp % 64) != 0 || nsplit < 1 || nsplit * dnp_nsub(H) > 16 || H > 8 || nsteps < 1 || !rows_ok ||
       !head->enc_w0 || !head->enc_w1 || (head->lang_kv && (!head->q_w || !head->out_w || !head->ln_g || !head->sem || head->S_lang <= 0)) ||
       !tail->pos_w0 || !tail->rot_w0 || !tail->coef_pos || !tail->coef_rot || (tail->cond_mask && !tail->cond_data)) {
-    set_error("a3d_dn_persist: bad argument (B=%d L=%d D=%d E=%d H=%d S=%d Sp=%d nsplit=%d stacks %d/%d/%d steps %d from t=%d)", B, L, D, E, H,
-              S, Sp, nsplit, n_traj, n_pos, n_rot, nsteps, t_first);
+    set_error("%s: bad argument (B=%d L=%d D=%d E=%d H=%d S=%d Sp=%d nsplit=%d stacks %d/%d/%d steps %d from %s=%d)", name, B, L, D, E, H,
+              S, Sp, nsplit, n_traj, n_pos, n_rot, nsteps, row_label, row_first);
     return A3D_ERR_ARG;
   }
   if (head->lang_kv && (size_t)head->S_lang * 2 * E > (size_t)DR * (LDQK + LDH) + DN_PS) {
-    set_error("a3d_dn_persist: %d instruction tokens do not fit the LDS staging", head->S_lang);
+    set_error("%s: %d instruction tokens do not fit the LDS staging", name, head->S_lang);
     return A3D_ERR_ARG;
   }
   static int n_cu = 0;
@@ -1821,7 +1829,7 @@ extern "C" int a3d_dn_persist(const a3d_dn_layer_params* layers_dev, int n_traj,
   // every workgroup must be resident at once (the roles wait for each other): one workgroup per CU (121 KB of LDS each)
   const int nworkers = n_cu - 2 * U;                  // two sample-role workgroups per unit (primary + rotation-stack helper)
   if (n_cu <= 0 || nworkers < 16) {
-    set_error("a3d_dn_persist: %d trajectories x %d row tiles x 2 roles leave %d of %d CUs for the streaming role (>= 16 needed)", B, NT,
+    set_error("%s: %d trajectories x %d row tiles x 2 roles leave %d of %d CUs for the streaming role (>= 16 needed)", name, B, NT,
               nworkers, n_cu);
     return A3D_ERR_ARG;
   }
@@ -1832,7 +1840,8 @@ extern "C" int a3d_dn_persist(const a3d_dn_layer_params* layers_dev, int n_traj,
   a.tail = *tail;
   a.traj = traj; a.qbuf = qbuf; a.part = part; a.sync = sync; a.kvx = kvx; a.xbuf = xbuf;
   a.B = B; a.L = L; a.NT = NT; a.D = D; a.E = E; a.H = H; a.S = S; a.Sp = Sp; a.nsplit = nsplit; a.nsub = dnp_nsub(H);
-  a.n_traj = n_traj; a.n_pos = n_pos; a.n_rot = n_rot; a.t_first = t_first; a.nsteps = nsteps;
+  a.n_traj = n_traj; a.n_pos = n_pos; a.n_rot = n_rot; a.nsteps = nsteps;
+  a.row_first = row_first; a.row_inc = row_inc; a.term_row = term_row;
   a.prof = (dn_warm() & 2) ? reinterpret_cast<long long*>(sync + words + ((sizeof(DnPersist) + 15) / 16) * 4) : nullptr;
   a.spin_limit = 1 << 21;                     // ~2 s of polling: a wait is at most a few milliseconds; beyond it the launch aborts
   if (const char* sl = getenv("A3D_DN_SPIN_LIMIT")) a.spin_limit = atoi(sl);      // test hook: 0 forces the abort path (tests/test_diffusion_gpu.py)
@@ -1854,16 +1863,43 @@ extern "C" int a3d_dn_persist(const a3d_dn_layer_params* layers_dev, int n_traj,
   return check_launch("a3d_dn_persist(poison)");
 }
 
-extern "C" int a3d_dn_tail(const float* pos_feats, const float* rot_feats, const float* traj, int D,
-                           const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int t_step, void* stream) {
+extern "C" int a3d_dn_persist(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot, const a3d_dn_head_params* head,
+                              const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
+                              int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int t_first, int nsteps, void* stream) {
+  return dnp_launch("a3d_dn_persist", layers_dev, n_traj, n_pos, n_rot, head, tail, traj, qbuf, part, kvx, xbuf, sync, B, L, D, E, H, S, Sp,
+                    nsplit, t_first, -1, 0, nsteps, t_first >= nsteps - 1, "t", stream);
+}
+
+extern "C" int a3d_dn_persist_sched(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot,
+                                    const a3d_dn_head_params* head, const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part,
+                                    float* kvx, float* xbuf, int* sync, int B, int L, int D, int E, int H, int S, int Sp, int nsplit,
+                                    int row_first, int nsteps, int n_rows, int last_terminal, void* stream) {
+  // rows row_first .. row_first + nsteps - 1 of tables that hold n_rows rows
+  const bool rows_ok = row_first >= 0 && n_rows >= 1 && nsteps <= n_rows && row_first <= n_rows - nsteps && (last_terminal == 0 || last_terminal == 1);
+  return dnp_launch("a3d_dn_persist_sched", layers_dev, n_traj, n_pos, n_rot, head, tail, traj, qbuf, part, kvx, xbuf, sync, B, L, D, E, H, S,
+                    Sp, nsplit, row_first, 1, last_terminal ? row_first + nsteps - 1 : -1, nsteps, rows_ok, "row", stream);
+}
+
+static int dn_tail_launch(const char* name, const float* pos_feats, const float* rot_feats, const float* traj, int D,
+                          const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int row, int terminal, void* stream) {
   if (!pos_feats || !rot_feats || !traj || !p || !traj_out || B <= 0 || L <= 0 || L > DR || E <= 0 || E > 128 || D < 4 || D > 16 ||
-      t_step < 0 || !p->pos_w0 || !p->rot_w0 || !p->coef_pos || !p->coef_rot || (p->cond_mask && !p->cond_data)) {
-    set_error("a3d_dn_tail: bad argument");
+      row < 0 || (terminal != 0 && terminal != 1) || !p->pos_w0 || !p->rot_w0 || !p->coef_pos || !p->coef_rot || (p->cond_mask && !p->cond_data)) {
+    set_error("%s: bad argument", name);
     return A3D_ERR_ARG;
   }
   hipLaunchKernelGGL(dn_tail_kernel, dim3(B), dim3(dn_threads()), 0, (hipStream_t)stream, pos_feats, rot_feats, traj, D, *p, traj_out, L,
-                     E, t_step, dn_warm());
-  return check_launch("a3d_dn_tail");
+                     E, row, terminal, dn_warm());
+  return check_launch(name);
+}
+
+extern "C" int a3d_dn_tail(const float* pos_feats, const float* rot_feats, const float* traj, int D,
+                           const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int t_step, void* stream) {
+  return dn_tail_launch("a3d_dn_tail", pos_feats, rot_feats, traj, D, p, traj_out, B, L, E, t_step, t_step == 0, stream);
+}
+
+extern "C" int a3d_dn_tail_sched(const float* pos_feats, const float* rot_feats, const float* traj, int D,
+                                 const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int row, int terminal, void* stream) {
+  return dn_tail_launch("a3d_dn_tail_sched", pos_feats, rot_feats, traj, D, p, traj_out, B, L, E, row, terminal, stream);
 }
 
 extern "C" int a3d_rope_rows_f32(const float* Y, int ldy, const float* xyz, const float* freq, float scale, float* out, int B,

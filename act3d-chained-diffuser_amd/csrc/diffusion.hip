@@ -6,6 +6,8 @@
 //                        their own schedules                                   diffusion_model.py:296-305
 //   a3d_ddpm_step        inpaint (out[mask] = cond[mask]) + DDPMScheduler.step with prediction_type="sample",
 //                        clip_sample, fixed_small variance                      diffusion_model.py:107-117
+//   a3d_ddpm_step_sched  the same update x_prev = c0 clip(x0) + c1 x_t + c2 z on row `row` of tables indexed by step position
+//                        (strided DDPM / DDIM sampler schedules), with an explicit terminal flag instead of t == 0
 //   a3d_adaln_{fwd,bwd}  x * (1 + scale) + shift                                layers.py:273-290
 //   a3d_sinusoidal_emb   [sin(x f_j) | cos(x f_j)]                              position_encodings.py:7-20
 //   a3d_silu_{fwd,bwd}   SiLU in AdaLN's modulation                             layers.py:276-278
@@ -29,19 +31,19 @@ __global__ void ddpm_add_noise_kernel(const float* __restrict__ x0, const float*
   }
 }
 
-// coef tables: [T][3] = (coef_x0, coef_xt, sigma) per schedule
+// coef tables: [rows][3] = (coef_x0, coef_xt, sigma) per schedule; terminal: the in-painted network output is the result
 __global__ void ddpm_step_kernel(const float* __restrict__ model_out, const float* __restrict__ sample,
                                  const float* __restrict__ noise, const float* __restrict__ cond_data,
                                  const unsigned char* __restrict__ cond_mask, const float* __restrict__ coef_pos,
                                  const float* __restrict__ coef_rot, float* __restrict__ out, int rows, int D,
-                                 int npos, int t) {
+                                 int npos, int row, int terminal) {
   const size_t total = (size_t)rows * D;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % D);
     float mo = model_out[i];
     if (cond_mask && cond_mask[i]) mo = cond_data[i];
-    if (t == 0) { out[i] = mo; continue; }
-    const float* cf = ((c < npos) ? coef_pos : coef_rot) + (size_t)t * 3;
+    if (terminal) { out[i] = mo; continue; }
+    const float* cf = ((c < npos) ? coef_pos : coef_rot) + (size_t)row * 3;
     const float x0 = fminf(fmaxf(mo, -1.0f), 1.0f);
     float prev = cf[0] * x0 + cf[1] * sample[i];
     if (noise) prev += cf[2] * noise[i];
@@ -304,8 +306,16 @@ extern "C" int a3d_ddpm_step(const float* model_out, const float* sample, const 
                              const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out,
                              int rows, int D, int npos, int t, void* stream) {
   if (!model_out || !sample || !coef_pos || !coef_rot || !out || rows <= 0 || D <= 0 || t < 0 || (cond_mask && !cond_data)) { set_error("a3d_ddpm_step: bad argument"); return A3D_ERR_ARG; }
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, t);
+  hipLaunchKernelGGL(ddpm_step_kernel, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, t, t == 0);
   return check_launch("a3d_ddpm_step");
+}
+extern "C" int a3d_ddpm_step_sched(const float* model_out, const float* sample, const float* noise, const float* cond_data,
+                                   const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out,
+                                   int rows, int D, int npos, int row, int terminal, void* stream) {
+  if (!model_out || !sample || !coef_pos || !coef_rot || !out || rows <= 0 || D <= 0 || row < 0 || (terminal != 0 && terminal != 1) ||
+      (cond_mask && !cond_data)) { set_error("a3d_ddpm_step_sched: bad argument"); return A3D_ERR_ARG; }
+  hipLaunchKernelGGL(ddpm_step_kernel, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, row, terminal);
+  return check_launch("a3d_ddpm_step_sched");
 }
 extern "C" int a3d_adaln_fwd(const float* x, const float* mod, float* y, int B, int L, int E, void* stream) {
   if (!x || !mod || !y || B <= 0 || L <= 0 || E <= 0) { set_error("a3d_adaln_fwd: bad argument"); return A3D_ERR_ARG; }

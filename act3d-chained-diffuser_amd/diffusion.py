@@ -52,17 +52,78 @@ class DDPMTables:
         self.coef_pos, self.coef_rot = self._coef(acp_pos).to(device), self._coef(acp_rot).to(device)
 
     def _coef(self, acp):
-        one = torch.tensor(1.0)
-        rows = []
-        for t in range(self.T):
-            a_t, a_prev = acp[t], (acp[t - 1] if t > 0 else one)
+        return sampler_coefficients(acp, range(self.T), 1).float().contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ sampler schedules
+SCHEDULERS = ("ddpm", "ddim")
+
+
+def check_sampler_args(T, num_inference_steps=None, scheduler="ddpm", eta=0.0):
+    """Validates the sampler-schedule arguments of compute_trajectory on the host; returns K (None -> T)."""
+    if scheduler not in SCHEDULERS:
+        raise ValueError("unknown scheduler %r (one of %s)" % (scheduler, ", ".join(SCHEDULERS)))
+    K = T if num_inference_steps is None else num_inference_steps
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= T:
+        raise ValueError("num_inference_steps must be an integer in [1, %d], got %r" % (T, num_inference_steps))
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError("eta must lie in [0, 1], got %r" % (eta,))
+    if scheduler == "ddpm" and float(eta) != 0.0:
+        raise ValueError("eta = %r needs scheduler='ddim' (the ancestral DDPM sampler has no eta)" % (eta,))
+    return K
+
+
+def sampler_timesteps(T, K):
+    """'Leading' spacing: stride r = T // K, t_i = (K - 1 - i) r for i = 0 .. K - 1; the last one is always 0.  Returns (list, r)."""
+    r = T // K
+    return [(K - 1 - i) * r for i in range(K)], r
+
+
+def sampler_coefficients(acp, timesteps, stride, scheduler="ddpm", eta=0.0):
+    """Rows (c0, c1, c2) of the update  x_prev = c0 clip(x0, -1, 1) + c1 x_t + c2 z  at the given timesteps, in acp's dtype;
+    the step from t lands on prev = t - stride with a_prev = acp[prev], or 1 when prev < 0 (c2 = 0 there: no noise at the end).
+    "ddpm": the posterior of Ho et al. 2020 eq. 6-7 between t and prev, variance "fixed_small" clamped at 1e-20, in acp's own
+    arithmetic (with every timestep and stride 1 these are DDPMTables.coef_*, bit for bit).
+    "ddim": Song et al. 2021 eq. 12 with eps DERIVED FROM THE CLIPPED x0, eps = (x_t - sqrt(a_t) clip(x0)) / sqrt(1 - a_t) -- the
+    choice that keeps the update a three-coefficient form:  sigma = eta sqrt((1 - a_prev) / (1 - a_t)) sqrt(1 - a_t / a_prev),
+    c1 = sqrt(1 - a_prev - sigma^2) / sqrt(1 - a_t),  c0 = sqrt(a_prev) - c1 sqrt(a_t),  c2 = sigma; evaluated in float64."""
+    rows = []
+    for t in timesteps:
+        prev = t - stride
+        if scheduler == "ddpm":
+            a_t, a_prev = acp[t], (acp[prev] if prev >= 0 else torch.ones((), dtype=acp.dtype))
             b_t, b_prev = 1 - a_t, 1 - a_prev
             cur_a = a_t / a_prev
             cur_b = 1 - cur_a
             var = torch.clamp(b_prev / b_t * cur_b, min=1e-20)
             rows.append(torch.stack([(a_prev ** 0.5 * cur_b) / b_t, cur_a ** 0.5 * b_prev / b_t,
-                                     var ** 0.5 if t > 0 else torch.tensor(0.0)]))
-        return torch.stack(rows).float().contiguous()
+                                     var ** 0.5 if prev >= 0 else torch.zeros((), dtype=acp.dtype)]))
+        else:
+            a_t = acp[t].double()
+            a_prev = acp[prev].double() if prev >= 0 else torch.ones((), dtype=torch.float64)
+            sigma = float(eta) * ((1 - a_prev) / (1 - a_t)) ** 0.5 * (1 - a_t / a_prev) ** 0.5
+            c1 = torch.clamp(1 - a_prev - sigma ** 2, min=0.0) ** 0.5 / (1 - a_t) ** 0.5
+            rows.append(torch.stack([a_prev ** 0.5 - c1 * a_t ** 0.5, c1, sigma]).to(acp.dtype))
+    return torch.stack(rows)
+
+
+class SamplerSchedule:
+    """A K-step sampler over the T training timesteps of a DDPMTables (its position and rotation schedules): the timestep list and
+    the per-step coefficient tables coef_pos / coef_rot [K][3], indexed by step POSITION i (the i-th executed step), see
+    sampler_timesteps / sampler_coefficients.  The step at timestep 0 (position K - 1) is terminal for both schedulers: it returns
+    the in-painted network output and adds no noise, as the full chain does.  noise_free: no step reads a noise draw (DDIM, eta = 0)."""
+
+    def __init__(self, tables, num_inference_steps=None, scheduler="ddpm", eta=0.0):
+        self.T = tables.T
+        self.K = check_sampler_args(tables.T, num_inference_steps, scheduler, eta)
+        self.scheduler, self.eta = scheduler, float(eta)
+        self.timesteps, self.stride = sampler_timesteps(self.T, self.K)
+        dev = tables.acp_pos.device
+        self.coef_pos, self.coef_rot = (
+            sampler_coefficients(acp.cpu(), self.timesteps, self.stride, scheduler, eta).float().contiguous().to(dev)
+            for acp in (tables.acp_pos, tables.acp_rot))
+        self.noise_free = scheduler == "ddim" and self.eta == 0.0
+        self.key = (self.K, scheduler, self.eta)
 
 
 # ------------------------------------------------------------------------------------------------ pose <-> signal
@@ -371,7 +432,8 @@ class DiffusionHead(nn.Module):
     def build_fused(self, ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=True):
         """Step-invariant state of the fused sampling path for one trajectory batch: the context K (fp16 hi | lo rows) / V (fp16
         hi / lo planes) of every cross-attention layer, the instruction tokens through traj_lang_attention's k | v projection, and
-        the AdaLN modulation of every layer at every timestep (Linear(SiLU(sinusoidal(t))), layers.py:273-290).  Returns
+        the AdaLN modulation of every layer at every row of time_sin (Linear(SiLU(sinusoidal(t))), layers.py:273-290): all T timesteps
+        for the full chain, only the K scheduled ones -- in step order -- under a SamplerSchedule.  Returns
         {"tensors": [...]} -- the list is what a captured graph must refresh in place -- plus per-layer pointer tables."""
         B, S, E = ctx.shape
         H = self.num_attn_heads
@@ -415,7 +477,8 @@ class DiffusionHead(nn.Module):
     def _build_persist(self, st, B, Ln, H, E, Sp, T, dev):
         """State of the persistent sampler (a3d_dn_persist: the whole denoise loop as one launch, csrc/denoise.hip): the device
         table of per-layer parameter blocks (AdaLN tables by their base: the kernel indexes them with the step), the query /
-        partial exchange buffers and the synchronisation words.  None when the batch leaves too few CUs for the streaming role."""
+        partial exchange buffers and the synchronisation words.  None when the batch leaves too few CUs for the streaming role.
+        T: rows of the AdaLN tables -- the training timesteps, or the K steps of a sampler schedule (a3d_dn_persist_sched)."""
         import ctypes
         Lb = O.L
         lib = Lb.load()
@@ -452,12 +515,15 @@ class DiffusionHead(nn.Module):
             "kvx": torch.empty((lib.a3d_dn_persist_kvx_floats(B, Ln, E),), device=dev, dtype=torch.float32) if NT > 1 else None,
             "sync": torch.zeros((lib.a3d_dn_persist_sync_ints(B, Ln, n_layers, T),), device=dev, dtype=torch.int32),
             "stacks": (len(self.traj_attention[0].layers), len(self.pos_attention[0].layers), len(self.rot_attention[0].layers)),
+            "rows": T,                                          # rows of the AdaLN tables = the most steps one launch may run
         }
 
     @torch.no_grad()
-    def fused_persist(self, st, traj, t_first, nsteps, step_noise, cond_data, cond_mask_u8, tb):
+    def fused_persist(self, st, traj, t_first, nsteps, step_noise, cond_data, cond_mask_u8, tb, sched=None):
         """nsteps consecutive denoise steps t_first, t_first - 1, ... (network evaluation + DDPM reverse step each) as ONE launch of
-        the persistent sampler; returns the trajectory after the last of them (a new tensor).  step_noise: the (T, B, L, D) table."""
+        the persistent sampler; returns the trajectory after the last of them (a new tensor).  step_noise: the (T, B, L, D) table.
+        sched (a SamplerSchedule; st built on its timesteps): the steps at POSITIONS t_first, t_first + 1, ... of the schedule
+        (a3d_dn_persist_sched); step_noise is then (K, B, L, D) by position, or None for a noise-free schedule."""
         Lb = O.L
         ps = st["persist"]
         B, Ln, D = traj.shape
@@ -475,24 +541,33 @@ class DiffusionHead(nn.Module):
         pr, rr = self.pos_regressor[0], self.rot_regressor[0]
         tp = Lb.DnTailParams(pos_w0=pr[0].weight.data_ptr(), pos_b0=pr[0].bias.data_ptr(), pos_w1=pr[3].weight.data_ptr(),
                              pos_b1=pr[3].bias.data_ptr(), rot_w0=rr[0].weight.data_ptr(), rot_b0=rr[0].bias.data_ptr(),
-                             rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(), noise=step_noise.data_ptr(),
+                             rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(),
+                             noise=None if step_noise is None else step_noise.data_ptr(),
                              cond_data=cond_data.data_ptr(), cond_mask=cond_mask_u8.data_ptr(), coef_pos=tb.coef_pos.data_ptr(),
                              coef_rot=tb.coef_rot.data_ptr())
         out = traj.clone()
         self._last_persist = ps                      # tests read the abort word (sync[2]) after synchronising
         nt, npos, nrot = ps["stacks"]
-        Lb.call("a3d_dn_persist", ps["table"].data_ptr(), nt, npos, nrot, C_byref(hp), C_byref(tp), out.data_ptr(), ps["qbuf"].data_ptr(),
-                ps["part"].data_ptr(), None if ps["kvx"] is None else ps["kvx"].data_ptr(), ps["xbuf"].data_ptr(), ps["sync"].data_ptr(),
-                B, Ln, D, E, H, st["S"], st["Sp"], ps["nsplit"], int(t_first), int(nsteps),
-                Lb.stream())
+        common = (ps["table"].data_ptr(), nt, npos, nrot, C_byref(hp), C_byref(tp), out.data_ptr(), ps["qbuf"].data_ptr(),
+                  ps["part"].data_ptr(), None if ps["kvx"] is None else ps["kvx"].data_ptr(), ps["xbuf"].data_ptr(), ps["sync"].data_ptr(),
+                  B, Ln, D, E, H, st["S"], st["Sp"], ps["nsplit"], int(t_first), int(nsteps))
+        if sched is None:
+            entry = "a3d_dn_persist"
+            Lb.call(entry, *common, Lb.stream())
+        else:
+            entry = "a3d_dn_persist_sched"
+            assert tb is sched and ps["rows"] == sched.K and (step_noise is None) == sched.noise_free
+            Lb.call(entry, *common, sched.K, int(t_first + nsteps == sched.K), Lb.stream())
         if DN_PERSIST_CHECK:
             if int(ps["sync"][2].item()) != 0:
-                raise RuntimeError("a3d_dn_persist gave up waiting (sync[2] != 0): the trajectory is invalid")
+                raise RuntimeError(entry + " gave up waiting (sync[2] != 0): the trajectory is invalid")
         return out
 
     @torch.no_grad()
-    def fused_step(self, st, traj, t, noise, cond_data, cond_mask_u8, tb):
-        """One denoise step: network evaluation at timestep t + DDPM reverse step -> the next trajectory (B, L, D)."""
+    def fused_step(self, st, traj, t, noise, cond_data, cond_mask_u8, tb, terminal=None):
+        """One denoise step: network evaluation at timestep t + DDPM reverse step -> the next trajectory (B, L, D).
+        terminal (bool) given: t is the step's POSITION in a SamplerSchedule (st and tb built on it) and terminal says whether the
+        step returns the in-painted network output (a3d_dn_tail_sched)."""
         Lb = O.L
         out = torch.empty_like(traj)
         B, Ln, D = traj.shape
@@ -565,8 +640,12 @@ class DiffusionHead(nn.Module):
                              rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(), noise=nz(noise),
                              cond_data=cond_data.data_ptr(), cond_mask=cond_mask_u8.data_ptr(), coef_pos=tb.coef_pos.data_ptr(),
                              coef_rot=tb.coef_rot.data_ptr())
-        Lb.call("a3d_dn_tail", pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, C_byref(tp), out.data_ptr(), B, Ln, E,
-                int(t), stream)
+        if terminal is None:
+            Lb.call("a3d_dn_tail", pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, C_byref(tp), out.data_ptr(), B, Ln, E,
+                    int(t), stream)
+        else:
+            Lb.call("a3d_dn_tail_sched", pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, C_byref(tp), out.data_ptr(), B, Ln, E,
+                    int(t), int(bool(terminal)), stream)
         return out
 
 
@@ -630,7 +709,19 @@ class DiffusionPlanner(nn.Module):
             E = self.prediction_head.curr_gripper_embed.weight.shape[1]
             sin = O.sinusoidal_emb(torch.arange(self.n_steps, device=device, dtype=torch.float32), E)
             self._time_tables = {"sin": sin, "silu": F.silu(sin)}
+            self._schedules = {}
         return self._tables
+
+    def schedule(self, device, num_inference_steps=None, scheduler="ddpm", eta=0.0):
+        """The SamplerSchedule of (K, scheduler, eta) on `device` (built once and kept: a captured graph addresses its tables),
+        with time_sin = the sinusoidal embedding rows of its K timesteps in step order."""
+        tb = self.tables(device)
+        key = (check_sampler_args(self.n_steps, num_inference_steps, scheduler, eta), scheduler, float(eta))
+        if key not in self._schedules:
+            sc = SamplerSchedule(tb, *key)
+            sc.time_sin = self._time_tables["sin"][torch.tensor(sc.timesteps, device=device)].contiguous()
+            self._schedules[key] = sc
+        return self._schedules[key]
 
     def normalize_pos(self, pos):
         lo, hi = self.gripper_loc_bounds[0], self.gripper_loc_bounds[1]
@@ -701,11 +792,24 @@ class DiffusionPlanner(nn.Module):
     @torch.no_grad()
     def compute_trajectory(self, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, *,
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
-                           return_trace=False, fused=None):
+                           return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0):
+        """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
+        num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
+        timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
+        i used by the i-th executed step, and is neither drawn nor read for "ddim" with eta = 0.  n_steps truncates the (scheduled)
+        step list for fixtures; a truncated run has no terminal step."""
         head = self.prediction_head
         dev = pcd_obs.device
-        tb = self.tables(dev)
         B, Ln = trajectory_mask.shape
+        # host-side checks first: bad schedule arguments raise before anything is launched
+        scheduled = num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0
+        if scheduled:
+            K = check_sampler_args(self.n_steps, num_inference_steps, scheduler, eta)
+            if step_noise is not None and step_noise.shape[0] != K:
+                raise ValueError("step_noise has %d leading rows for a schedule of %d steps (one row per step position)"
+                                 % (step_noise.shape[0], K))
+        tb = self.tables(dev)
+        sched = self.schedule(dev, K, scheduler, eta) if scheduled else None
         tokens, ctx_xyz, cg, gg = self._prepare(rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens)
         multi = head.attn_rounds * head.feat_scales > 1
         if not multi:
@@ -725,12 +829,18 @@ class DiffusionPlanner(nn.Module):
         cond_data = cond_data.contiguous()
         if init_noise is None:
             init_noise = torch.randn((B, Ln, D), device=dev)
-        if step_noise is None:
-            step_noise = torch.randn((self.n_steps, B, Ln, D), device=dev)
-        step_noise = step_noise.to(dev).float().contiguous()
-        steps = list(range(self.n_steps - 1, -1, -1))
+        if sched is not None and sched.noise_free:
+            step_noise = None                               # DDIM with eta = 0: no draw is made, captured or read
+        else:
+            if step_noise is None:
+                step_noise = torch.randn((self.n_steps if sched is None else sched.K, B, Ln, D), device=dev)
+            step_noise = step_noise.to(dev).float().contiguous()
+        steps = list(range(self.n_steps - 1, -1, -1)) if sched is None else list(sched.timesteps)
         if n_steps is not None:
             steps = steps[:n_steps]
+        # tables of the DDPM-step kernels and of the AdaLN modulation: by timestep (full chain) or by step position (schedule)
+        time_sin = self._time_tables["sin"] if sched is None else sched.time_sin
+        sched_key = None if sched is None else sched.key
         traj = (init_noise.to(dev).float() + cond_data).contiguous()
         kmask = trajectory_mask.to(torch.uint8).contiguous()
         trace = []
@@ -751,8 +861,8 @@ class DiffusionPlanner(nn.Module):
             # sampler buffers (a ctypes table, a pageable host-to-device copy = a host sync, five allocations) that would be thrown away
             gr_ = self._graph
             reuse = (use_graph and not return_trace and gr_ is not None and gr_["key"][:3] == (B, Ln, tuple(steps)) and
-                     isinstance(gr_.get("state"), dict) and gr_["state"].get("persist") is not None)
-            state = head.build_fused(ctx, ctx_xyz, instr, kmask, self._time_tables["sin"], Ln, with_persist=not reuse)
+                     gr_["key"][-1] == sched_key and isinstance(gr_.get("state"), dict) and gr_["state"].get("persist") is not None)
+            state = head.build_fused(ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=not reuse)
             if reuse:
                 state["persist"] = gr_["state"]["persist"]
             static = list(state["tensors"])
@@ -765,14 +875,43 @@ class DiffusionPlanner(nn.Module):
             state = head.build_kv_cache(ctx, ctx_xyz, instr)
             static = [c[k] for c in state["ctx"] for k in ("Ks", "Vt")] + \
                 ([state["lang"]["Ks"], state["lang"]["Vt"]] if "lang" in state else [])
-        static = static + [step_noise, cond_data, cond_mask_u8, kmask]
+        static = static + ([] if step_noise is None else [step_noise]) + [cond_data, cond_mask_u8, kmask]
+        if sched is not None:
+            static = static + [sched.coef_pos, sched.coef_rot]
 
-        persist = fused and state.get("persist") is not None and all(a_ - b_ == 1 for a_, b_ in zip(steps, steps[1:]))
+        # the persistent sampler walks its tables row by row: consecutive timesteps of the full chain, or any schedule by position
+        in_order = sched is not None or all(a_ - b_ == 1 for a_, b_ in zip(steps, steps[1:]))
+        persist = fused and state.get("persist") is not None and in_order
         # which sampler serves this call (read by the bench line and the tests)
-        self.last_sampler_path = "multi-round" if multi else ("persistent (a3d_dn_persist)" if persist else
-                                                               ("per-phase fused launches" if fused else "op-by-op"))
+        self.last_sampler_path = "multi-round" if multi else (
+            ("persistent (a3d_dn_persist)" if sched is None else "persistent (a3d_dn_persist_sched)") if persist else
+            ("per-phase fused launches" if fused else "op-by-op"))
+
+        def run_scheduled(x):
+            # step position i is the row of every table; the step at timestep 0 (position K - 1) is terminal
+            if persist and not return_trace:
+                return head.fused_persist(state, x, 0, len(steps), step_noise, cond_data, cond_mask_u8, sched, sched=sched)
+            for i, t in enumerate(steps):
+                term = i == sched.K - 1
+                nz = None if (step_noise is None or term) else step_noise[i]
+                if multi:
+                    tt = torch.full((B,), t, device=dev, dtype=torch.long)
+                    out = head.forward_multi(x, tmask, tt, toks, xyzs, instruction, cg, gg)[-1]
+                    x = O.ddpm_step_sched(out, x, nz, cond_data, cond_mask_u8, sched.coef_pos, sched.coef_rot, i, term)
+                elif persist:
+                    x = head.fused_persist(state, x, i, 1, step_noise, cond_data, cond_mask_u8, sched, sched=sched)
+                elif fused:
+                    x = head.fused_step(state, x, i, nz, cond_data, cond_mask_u8, sched, terminal=term)
+                else:
+                    out = head.denoise_tokens_cached(x, kmask, t, state, self._time_tables)
+                    x = O.ddpm_step_sched(out, x, nz, cond_data, cond_mask_u8, sched.coef_pos, sched.coef_rot, i, term)
+                if return_trace:
+                    trace.append(x)
+            return x
 
         def run_loop(x):
+            if sched is not None:
+                return run_scheduled(x)
             if persist and not return_trace:                # the whole loop: one launch
                 return head.fused_persist(state, x, steps[0], len(steps), step_noise, cond_data, cond_mask_u8, tb)
             for t in steps:
@@ -793,11 +932,11 @@ class DiffusionPlanner(nn.Module):
             return x
 
         if use_graph and not return_trace:
-            key = (B, Ln, tuple(steps), fused, tuple((tuple(t_.shape), t_.dtype) for t_ in static))
+            key = (B, Ln, tuple(steps), fused, tuple((tuple(t_.shape), t_.dtype) for t_ in static), sched_key)
             if self._graph is not None and self._graph["key"] != key and fused and state.get("persist") is self._graph["state"].get("persist"):
                 # the shapes changed after all (another context size): this call needs its own persistent-sampler state
-                state["persist"] = head._build_persist(state, B, Ln, head.num_attn_heads, E, state["Sp"], self.n_steps, dev) if DN_PERSIST else None
-                persist = fused and state.get("persist") is not None and all(a_ - b_ == 1 for a_, b_ in zip(steps, steps[1:]))
+                state["persist"] = head._build_persist(state, B, Ln, head.num_attn_heads, E, state["Sp"], time_sin.shape[0], dev) if DN_PERSIST else None
+                persist = fused and state.get("persist") is not None and in_order
             if self._graph is None or self._graph["key"] != key:
                 static_in = traj.clone()
                 side = torch.cuda.Stream()

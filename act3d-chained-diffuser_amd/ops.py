@@ -1581,6 +1581,16 @@ def ddpm_step(model_out, sample, noise, cond_data, cond_mask_u8, coef_pos, coef_
     return out
 
 
+def ddpm_step_sched(model_out, sample, noise, cond_data, cond_mask_u8, coef_pos, coef_rot, row, terminal, out=None):
+    """ddpm_step on [K][3] tables indexed by step position (diffusion.SamplerSchedule): row = the step's position, terminal = the
+    step returns the in-painted network output."""
+    out = torch.empty_like(sample) if out is None else out
+    L.call("a3d_ddpm_step_sched", model_out.data_ptr(), sample.data_ptr(), None if noise is None else noise.data_ptr(),
+           cond_data.data_ptr(), cond_mask_u8.data_ptr(), coef_pos.data_ptr(), coef_rot.data_ptr(), out.data_ptr(),
+           sample.numel() // sample.shape[-1], sample.shape[-1], 3, int(row), int(bool(terminal)), L.stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ inference K/V cache
 def kv_cache_build(k_in, k_xyz, mha, H):
     """Step-invariant K/V operands of one cross-attention layer (context projected, rotated, split) -- computed once per

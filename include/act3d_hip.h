@@ -362,6 +362,12 @@ int a3d_ddpm_add_noise(const float* x0, const float* noise, const long long* t, 
 int a3d_ddpm_step(const float* model_out, const float* sample, const float* noise, const float* cond_data,
                   const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out, int rows,
                   int D, int npos, int t, void* stream);
+/* The same reverse step for a sampler schedule (strided DDPM, DDIM): coef_*: [K][3] device tables indexed by step POSITION, `row`
+ * the position of this step; terminal = 1: out = the in-painted model_out (today's t == 0 rule), else
+ * out = c0[row]*clip(model_out,-1,1) + c1[row]*sample + c2[row]*noise  (noise NULL: no noise term, e.g. DDIM with eta = 0). */
+int a3d_ddpm_step_sched(const float* model_out, const float* sample, const float* noise, const float* cond_data,
+                        const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out, int rows,
+                        int D, int npos, int row, int terminal, void* stream);
 /* AdaLN: y = x * (1 + mod[:, :E]) + mod[:, E:]  (layers.py:273-290); mod: [B][2E], x: [B][L][E]. */
 int a3d_adaln_fwd(const float* x, const float* mod, float* y, int B, int L, int E, void* stream);
 int a3d_adaln_bwd(const float* x, const float* mod, const float* dy, float* dx, float* dmod, int B, int L, int E,
@@ -439,6 +445,10 @@ int a3d_dn_rest(const float* x_in, const float* traj, int D, const float* ws, co
 /* regressors + trajectory update + DDPM reverse step t_step: traj ([B][L][D]) -> traj_out */
 int a3d_dn_tail(const float* pos_feats, const float* rot_feats, const float* traj, int D, const a3d_dn_tail_params* p,
                 float* traj_out, int B, int L, int E, int t_step, void* stream);
+/* a3d_dn_tail for a sampler schedule: p->coef_pos / coef_rot are [K][3] tables indexed by step position and `row` is this step's
+ * position; terminal = 1 returns the in-painted network output (a3d_dn_tail's t_step == 0), 0 applies row `row`. */
+int a3d_dn_tail_sched(const float* pos_feats, const float* rot_feats, const float* traj, int D, const a3d_dn_tail_params* p,
+                      float* traj_out, int B, int L, int E, int row, int terminal, void* stream);
 /* ---- persistent sampler: nsteps consecutive denoise steps t_first, t_first - 1, ... of one trajectory batch in ONE launch
  *      (diffusion_model.py:86-119: the loop body `out = prediction_head(...); trajectory = scheduler.step(...)`).  Two workgroup
  *      roles: TWO workgroups per (trajectory, 16-step row tile) run that unit's chain across layers AND steps -- the primary: head,
@@ -467,6 +477,18 @@ size_t a3d_dn_persist_sync_ints(int B, int L, int n_layers, int nsteps);
 int a3d_dn_persist(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot, const a3d_dn_head_params* head,
                    const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync, int B,
                    int L, int D, int E, int H, int S, int Sp, int nsplit, int t_first, int nsteps, void* stream);
+/* The persistent sampler on a sampler schedule (strided DDPM / DDIM: K << T network evaluations): the same kernel, buffers and
+ * limits as a3d_dn_persist, with every per-step table indexed by step POSITION instead of by timestep: cross.mod / rest.s_mod /
+ * rest.f_mod are the bases of [n_rows][2E] AdaLN tables (row i = the modulation at the i-th scheduled timestep), tail->coef_pos /
+ * coef_rot are [n_rows][3] (c0, c1, c2 of x_prev = c0 clip(x0) + c1 x_t + c2 z), tail->noise is the base of [n_rows][B][L][D] or
+ * NULL for a noise-free schedule.  The launch runs rows row_first, row_first + 1, ..., row_first + nsteps - 1 (all < n_rows);
+ * last_terminal = 1: the last of them is the terminal step (the in-painted network output is the result, as a3d_dn_persist does at
+ * t = 0), 0: every step applies its row.  sync: a3d_dn_persist_sync_ints(B, L, n_layers, nsteps) ints for the nsteps of the
+ * largest launch; sync[2] is the abort word as above. */
+int a3d_dn_persist_sched(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot, const a3d_dn_head_params* head,
+                         const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
+                         int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int row_first, int nsteps, int n_rows,
+                         int last_terminal, void* stream);
 /* development aid: 18 phase timestamps (100 MHz ticks) of workgroup 0 of the last a3d_dn_rest launch under A3D_DN_PROF=1 (host buffer) */
 int a3d_dbg_dn_prof(long long* out18);
 /* out[b][h][n][16] fp32 = rope3d(Y[b, n, :E] * scale, xyz) split into heads (column 15 and rows >= N zero): the K cache */
