@@ -992,6 +992,10 @@ struct DnPersist {
                                   // sample's row tiles (NT > 1 only; two buffers alternate from layer to layer)
   float* xbuf;                    // [U][2][16][128]: x after the trajectory stack (primary -> helper) | rotation features (helper -> primary)
   int B, L, NT, D, E, H, S, Sp, nsplit, nsub, n_traj, n_pos, n_rot, nsteps, spin_limit;
+  // Candidates per scene (a3d_dn_persist_group; 1 for the other entries): B counts TRAJECTORIES, trajectory j = scene n_cand + candidate
+  // belongs to scene j / n_cand, and everything context-sized (layers[].c.Kf / Vt, head.lang_kv) has B / n_cand samples and is
+  // indexed by scene.  Everything else (traj, noise, conditioning, kmask, qbuf, part, kvx, xbuf, the sync words) is per trajectory.
+  int n_cand;
   // Step `step` of the launch reads row  row_first + row_inc * step  of every per-step table (AdaLN modulation, posterior
   // coefficients, step noise); the step whose row is term_row is the terminal one (the in-painted network output is the result, no
   // reverse step).  a3d_dn_persist: tables by timestep, rows t_first, t_first - 1, ..., terminal at row 0 (row_inc -1, term_row 0);
@@ -1008,6 +1012,16 @@ constexpr int DNP_PROF_WORDS = 256;      // long longs: [0, 96) 32 items x {tick
 // are independent), so a step's chain is n_traj + max(n_pos, n_rot) layers deep instead of n_traj + n_pos + n_rot.  They hand
 // x over through xbuf (primary -> helper after the trajectory stack, helper -> primary after the rotation stack) with one flag each.
 // For the streamers a helper is just another unit: streaming unit id v = role * U + u (qbuf / partial / completion-counter slot).
+// A streaming GROUP = (role, scene, candidate chunk): the row tiles that share one K / V pass.  A chunk is dnp_chunk(NT) = max(1, 4 / NT)
+// consecutive candidates of the scene (the last chunk of a scene may be smaller), so a group never exceeds the four tiles
+// dnp_stream_item is instantiated for; its units are consecutive: v0 = role U0 + (scene n_cand + first candidate) NT, dnp_group_tiles of them.
+// Group id within a role: scene * dnp_nchunk + chunk.  With n_cand = 1 a group is a trajectory and has its NT tiles.
+__host__ __device__ __forceinline__ int dnp_chunk(int NT) { return NT >= 4 ? 1 : 4 / NT; }
+__host__ __device__ __forceinline__ int dnp_nchunk(int n_cand, int NT) { return (n_cand + dnp_chunk(NT) - 1) / dnp_chunk(NT); }
+__host__ __device__ __forceinline__ int dnp_group_tiles(int n_cand, int NT, int chunk) {
+  const int cs = dnp_chunk(NT), left = n_cand - chunk * cs;
+  return (left < cs ? left : cs) * NT;
+}
 constexpr int DNP_XDONE0 = 16;                      // sync words: [16 + 16 v] completion counter of streaming unit v < 2U
 __host__ __device__ __forceinline__ int dnp_kvdone0(int B, int NT) { return DNP_XDONE0 + 16 * 2 * B * NT; }          // [+ 16 (role B + b)]
 __host__ __device__ __forceinline__ int dnp_xtready0(int B, int NT) { return dnp_kvdone0(B, NT) + 16 * 2 * B; }      // [+ 16 u]
@@ -1064,7 +1078,8 @@ __device__ __forceinline__ int dnp_opaque(int v) {
   return __builtin_amdgcn_readfirstlane(v);          // uniform again (a scalar register) as far as the compiler is concerned
 }
 
-// One queue item: (role, sample bs, layer, key split) against ALL NTL row tiles of the trajectory (round 6; rounds 5's items were per
+// One queue item: (role, group, layer, key split) against ALL NTL row tiles of the group -- the tiles of one trajectory, or of a chunk
+// of candidate trajectories of one scene (units v0 .. v0 + NTL - 1; bs: the SCENE whose K / V slice is streamed) (round 6; rounds 5's items were per
 // tile, so that at the reference's horizon L = 50 every one of the 4 tiles streamed the sample's K / V slice separately: 4x the
 // algorithmic reads, 0.022 of the HBM roofline).  A wave (one head, one key sub-range) loads each 32-key fragment ONCE and runs the
 // NTL tiles' score / softmax / PV sequences against it -- independent instruction streams the scheduler interleaves.
@@ -1152,8 +1167,10 @@ __device__ __forceinline__ void dnp_stream_role(const DnPersist* ap, float* smem
   const int li = lane & 15, g = lane >> 4;
   const int NL = a.n_traj + a.n_pos + a.n_rot;
   const int U0 = a.B * a.NT, U = 2 * U0;            // U: streaming units (primaries + helpers)
-  const int G = 2 * a.B;                            // groups: (role, sample) = the NT row tiles that share one K / V pass
-  const long long total = (long long)a.nsteps * NL * a.B * a.nsplit;
+  const int n_cand = a.n_cand, cs = dnp_chunk(a.NT), nch = dnp_nchunk(n_cand, a.NT);
+  const int NG = (a.B / n_cand) * nch;              // groups per role: (scene, candidate chunk) = the row tiles that share one K / V pass
+  const int G = 2 * NG;
+  const long long total = (long long)a.nsteps * NL * NG * a.nsplit;
   const int nse = a.nsplit * a.nsub;
   float* Op = a.part;
   float* Mp = a.part + (size_t)nse * U * a.H * 256;
@@ -1177,13 +1194,15 @@ __device__ __forceinline__ void dnp_stream_role(const DnPersist* ap, float* smem
     __syncthreads();
     const int sp = sh[0], code = sh[1];
     if (sp < 0 || code == 0) break;
-    const int gl = (code - 1) / G, grp = (code - 1) - gl * G;        // gl: the layer; grp = role B + sample
-    const int role = grp / a.B, bs = grp - role * a.B;
-    const int v0 = role * U0 + bs * a.NT;                             // first streaming unit (row tile 0) of the group
+    const int gl = (code - 1) / G, grp = (code - 1) - gl * G;        // gl: the layer; grp = role NG + scene nch + chunk
+    const int role = grp / NG, gi = grp - role * NG;
+    const int bs = gi / nch, chunk = gi - bs * nch;                   // bs: the scene (context sample)
+    const int ntl = dnp_group_tiles(n_cand, a.NT, chunk);             // the group's own tile count (<= 4)
+    const int v0 = role * U0 + (bs * n_cand + chunk * cs) * a.NT;     // first streaming unit (row tile 0 of the chunk's first candidate)
     const a3d_dn_cross_params& c = dnp_args(ap).layers[gl].c;
     if (wave < a.H * a.nsub) {
       long long* pmark = (a.prof && (int)blockIdx.x == U && nprof < 14) ? a.prof + 208 + 3 * nprof : nullptr;     // prof words [208, 250)
-      switch (a.NT) {
+      switch (ntl) {
         case 1: dnp_stream_item<1>(a, c, bs, v0, sp, Op, Mp, wave, li, g, pmark); break;
         case 2: dnp_stream_item<2>(a, c, bs, v0, sp, Op, Mp, wave, li, g, pmark); break;
         case 3: dnp_stream_item<3>(a, c, bs, v0, sp, Op, Mp, wave, li, g, pmark); break;
@@ -1191,7 +1210,7 @@ __device__ __forceinline__ void dnp_stream_role(const DnPersist* ap, float* smem
       }
     }
     __syncthreads();
-    if (t < a.NT) __hip_atomic_fetch_add(&a.sync[DNP_XDONE0 + 16 * (v0 + t)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t < ntl) __hip_atomic_fetch_add(&a.sync[DNP_XDONE0 + 16 * (v0 + t)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (t == 0 && a.prof && (int)blockIdx.x == U && nprof < 32) { a.prof[nprof * 3 + 2] = wall_clock64(); ++nprof; }
   }
 }
@@ -1405,7 +1424,7 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
         // instruction k | v rows -> LDS: float4 loads, eight in flight per thread (the plain element loop issued one dependent
         // global load per iteration: 25 round trips, most of the 56 us the phase probe showed for the head)
         {
-          const float4* kv4 = reinterpret_cast<const float4*>(p.lang_kv + (size_t)bs * p.S_lang * 2 * E);      // rows of 2E floats: 16-byte aligned
+          const float4* kv4 = reinterpret_cast<const float4*>(p.lang_kv + (size_t)(bs / a.n_cand) * p.S_lang * 2 * E);      // the SCENE's rows of 2E floats: 16-byte aligned
           const int n4 = (p.S_lang * 2 * E) >> 2;
           for (int i0 = 0; i0 < n4; i0 += 8 * (int)blockDim.x) {
             float4 v[8];
@@ -1455,14 +1474,18 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
         }
         __syncthreads();
         if (t == 0) {
-          // the NT row tiles of a (role, sample) share one K / V pass: whoever publishes last queues the group's item.  (The tiles
-          // of a sample advance layer by layer together -- each needs the group's item of layer l to finish layer l -- so the
-          // k-th multiple of NT is the k-th layer of this role's stacks.)
-          const int grp = role * a.B + bs;
+          // the row tiles of a group (role, scene, candidate chunk) share one K / V pass: whoever publishes last queues the group's
+          // item.  (The tiles of a group advance layer by layer together -- each needs the group's item of layer l to finish
+          // layer l, whether they belong to one trajectory or to several candidates -- so the k-th multiple of the group's tile
+          // count is the k-th layer of this role's stacks.)
+          const int n_cand = a.n_cand, nch = dnp_nchunk(n_cand, NT);
+          const int scene = bs / n_cand, chunk = (bs - scene * n_cand) / dnp_chunk(NT);
+          const int NG = (a.B / n_cand) * nch;
+          const int grp = role * NG + scene * nch + chunk;
           const int cnt = __hip_atomic_fetch_add(&a.sync[dnp_grp0(a.B, NT) + 16 * grp], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-          if (cnt % NT == 0) {
+          if (cnt % dnp_group_tiles(n_cand, NT, chunk) == 0) {
             const int slot = atomicAdd(&a.sync[1], 1);
-            __hip_atomic_store(&a.sync[dnp_queue0(a.B, NT) + slot], 1 + l * (2 * a.B) + grp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&a.sync[dnp_queue0(a.B, NT) + slot], 1 + l * (2 * NG) + grp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
       }
@@ -1796,15 +1819,37 @@ extern "C" int a3d_dn_persist_prof(const int* sync, int B, int L, int n_layers, 
   return A3D_OK;
 }
 
-// Both entry points of the persistent sampler: `name` labels the error strings, rows_ok is the entry's own check of its step
+// Host mirror of the kernel's group algebra (the same dnp_chunk / dnp_nchunk / dnp_group_tiles the two roles evaluate), for the tests:
+// trajectory `traj` of B = scenes x n_cand trajectories of L steps -> out5 = {groups per role, the trajectory's group within a role,
+// the group's first unit (u = trajectory * NT + tile), the group's tile count, the trajectory's scene}
+extern "C" int a3d_dn_persist_group_of(int B, int L, int n_cand, int traj, int* out5) {
+  if (!out5 || B <= 0 || L <= 0 || L > 4 * DR || n_cand < 1 || B % n_cand != 0 || traj < 0 || traj >= B) {
+    set_error("a3d_dn_persist_group_of: bad argument (B=%d L=%d n_cand=%d traj=%d)", B, L, n_cand, traj);
+    return A3D_ERR_ARG;
+  }
+  const int NT = (L + DR - 1) / DR, nch = dnp_nchunk(n_cand, NT);
+  const int scene = traj / n_cand, chunk = (traj - scene * n_cand) / dnp_chunk(NT);
+  out5[0] = (B / n_cand) * nch;
+  out5[1] = scene * nch + chunk;
+  out5[2] = (scene * n_cand + chunk * dnp_chunk(NT)) * NT;
+  out5[3] = dnp_group_tiles(n_cand, NT, chunk);
+  out5[4] = scene;
+  return A3D_OK;
+}
+
+// All entry points of the persistent sampler: n_cand candidates per scene (1 but for a3d_dn_persist_group), `name` labels the error strings, rows_ok is the entry's own check of its step
 // arguments, (row_first, row_inc, term_row) is the table addressing of DnPersist.
 static int dnp_launch(const char* name, const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot, const a3d_dn_head_params* head,
                       const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
                       int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int row_first, int row_inc, int term_row, int nsteps,
-                      bool rows_ok, const char* row_label, void* stream) {
+                      bool rows_ok, const char* row_label, int n_cand, void* stream) {
   int rc = A3D_OK;
   if (B <= 0 || L <= 0 || L > 4 * DR || E <= 0 || E > 128 || (E % 6) != 0 || H * HD != E) {
     set_error("%s: bad shape (B=%d L=%d E=%d H=%d; L <= 64, E = 15 H <= 128)", name, B, L, E, H);
+    return A3D_ERR_ARG;
+  }
+  if (n_cand < 1 || B % n_cand != 0) {
+    set_error("%s: bad candidate count (n_cand=%d for B=%d trajectories; n_cand >= 1 and B = scenes x n_cand)", name, n_cand, B);
     return A3D_ERR_ARG;
   }
   const int NT = (L + DR - 1) / DR, U = B * NT;
@@ -1829,8 +1874,8 @@ static int dnp_launch(const char* name, const a3d_dn_layer_params* layers_dev, i
   // every workgroup must be resident at once (the roles wait for each other): one workgroup per CU (121 KB of LDS each)
   const int nworkers = n_cu - 2 * U;                  // two sample-role workgroups per unit (primary + rotation-stack helper)
   if (n_cu <= 0 || nworkers < 16) {
-    set_error("%s: %d trajectories x %d row tiles x 2 roles leave %d of %d CUs for the streaming role (>= 16 needed)", name, B, NT,
-              nworkers, n_cu);
+    set_error("%s: %d trajectories (%d candidates per scene) x %d row tiles x 2 roles leave %d of %d CUs for the streaming role "
+              "(>= 16 needed): per-phase entry points or fewer trajectories per call", name, B, n_cand, NT, nworkers, n_cu);
     return A3D_ERR_ARG;
   }
   const size_t words = dnp_words(B, L, n_traj + n_pos + n_rot, nsteps);
@@ -1840,7 +1885,7 @@ static int dnp_launch(const char* name, const a3d_dn_layer_params* layers_dev, i
   a.tail = *tail;
   a.traj = traj; a.qbuf = qbuf; a.part = part; a.sync = sync; a.kvx = kvx; a.xbuf = xbuf;
   a.B = B; a.L = L; a.NT = NT; a.D = D; a.E = E; a.H = H; a.S = S; a.Sp = Sp; a.nsplit = nsplit; a.nsub = dnp_nsub(H);
-  a.n_traj = n_traj; a.n_pos = n_pos; a.n_rot = n_rot; a.nsteps = nsteps;
+  a.n_traj = n_traj; a.n_pos = n_pos; a.n_rot = n_rot; a.nsteps = nsteps; a.n_cand = n_cand;
   a.row_first = row_first; a.row_inc = row_inc; a.term_row = term_row;
   a.prof = (dn_warm() & 2) ? reinterpret_cast<long long*>(sync + words + ((sizeof(DnPersist) + 15) / 16) * 4) : nullptr;
   a.spin_limit = 1 << 21;                     // ~2 s of polling: a wait is at most a few milliseconds; beyond it the launch aborts
@@ -1867,7 +1912,7 @@ extern "C" int a3d_dn_persist(const a3d_dn_layer_params* layers_dev, int n_traj,
                               const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
                               int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int t_first, int nsteps, void* stream) {
   return dnp_launch("a3d_dn_persist", layers_dev, n_traj, n_pos, n_rot, head, tail, traj, qbuf, part, kvx, xbuf, sync, B, L, D, E, H, S, Sp,
-                    nsplit, t_first, -1, 0, nsteps, t_first >= nsteps - 1, "t", stream);
+                    nsplit, t_first, -1, 0, nsteps, t_first >= nsteps - 1, "t", 1, stream);
 }
 
 extern "C" int a3d_dn_persist_sched(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot,
@@ -1877,7 +1922,17 @@ extern "C" int a3d_dn_persist_sched(const a3d_dn_layer_params* layers_dev, int n
   // rows row_first .. row_first + nsteps - 1 of tables that hold n_rows rows
   const bool rows_ok = row_first >= 0 && n_rows >= 1 && nsteps <= n_rows && row_first <= n_rows - nsteps && (last_terminal == 0 || last_terminal == 1);
   return dnp_launch("a3d_dn_persist_sched", layers_dev, n_traj, n_pos, n_rot, head, tail, traj, qbuf, part, kvx, xbuf, sync, B, L, D, E, H, S,
-                    Sp, nsplit, row_first, 1, last_terminal ? row_first + nsteps - 1 : -1, nsteps, rows_ok, "row", stream);
+                    Sp, nsplit, row_first, 1, last_terminal ? row_first + nsteps - 1 : -1, nsteps, rows_ok, "row", 1, stream);
+}
+
+// a3d_dn_persist_sched for B = scenes x n_cand candidate trajectories that share the scenes' context K / V cache and instruction rows
+extern "C" int a3d_dn_persist_group(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot,
+                                    const a3d_dn_head_params* head, const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part,
+                                    float* kvx, float* xbuf, int* sync, int B, int L, int D, int E, int H, int S, int Sp, int nsplit,
+                                    int row_first, int nsteps, int n_rows, int last_terminal, int n_cand, void* stream) {
+  const bool rows_ok = row_first >= 0 && n_rows >= 1 && nsteps <= n_rows && row_first <= n_rows - nsteps && (last_terminal == 0 || last_terminal == 1);
+  return dnp_launch("a3d_dn_persist_group", layers_dev, n_traj, n_pos, n_rot, head, tail, traj, qbuf, part, kvx, xbuf, sync, B, L, D, E, H, S,
+                    Sp, nsplit, row_first, 1, last_terminal ? row_first + nsteps - 1 : -1, nsteps, rows_ok, "row", n_cand, stream);
 }
 
 static int dn_tail_launch(const char* name, const float* pos_feats, const float* rot_feats, const float* traj, int D,

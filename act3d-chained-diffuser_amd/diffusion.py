@@ -14,7 +14,8 @@ What is restructured, with identical results:
     captured in a hipGraph and replayed (`compute_trajectory(..., use_graph=True)`).
 The DDPM schedules restate diffusers' DDPMScheduler (third-party, un-pinned -> parity unpinned).
 Additive keyword arguments: `noise`, `timesteps` (training) and `init_noise`, `step_noise` (sampling) inject the random
-draws; `visual_tokens` bypasses the backbone + FPN.  Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
+draws; `visual_tokens` bypasses the backbone + FPN; `num_inference_steps` / `scheduler` / `eta` select a few-step sampler
+schedule; `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8).  Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
 attention weights, residual branches, FFN -- and in the traj_encoder / regressor MLPs: layers.py:10,
 diffusion_head.py:46,183,193) runs on a device-resident Philox stream (csrc/dropout.hip, attention kernels): same
 distribution as the reference's torch generator, not the same draws.  The additive constructor keyword `dropout`
@@ -71,6 +72,21 @@ def check_sampler_args(T, num_inference_steps=None, scheduler="ddpm", eta=0.0):
     if scheduler == "ddpm" and float(eta) != 0.0:
         raise ValueError("eta = %r needs scheduler='ddim' (the ancestral DDPM sampler has no eta)" % (eta,))
     return K
+
+
+def check_num_samples(num_samples):
+    """Validates compute_trajectory's num_samples (candidates per scene) on the host; returns it as an int."""
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+        raise ValueError("num_samples must be an integer >= 1 (or None for one trajectory per scene), got %r" % (num_samples,))
+    return int(num_samples)
+
+
+def check_candidate_noise(init_noise, step_noise, B, G, Ln, D, rows):
+    """Shapes of the injected draws of a multi-candidate call: init_noise (B, G, L, D), step_noise (rows, B, G, L, D)."""
+    for name, x, want in (("init_noise", init_noise, (B, G, Ln, D)), ("step_noise", step_noise, (rows, B, G, Ln, D))):
+        if x is not None and tuple(x.shape) != want:
+            raise ValueError("%s has shape %s; num_samples=%d needs %s (%s)" % (
+                name, tuple(x.shape), G, want, "B, G, L, D" if len(want) == 4 else "steps, B, G, L, D"))
 
 
 def sampler_timesteps(T, K):
@@ -429,12 +445,15 @@ class DiffusionHead(nn.Module):
 
     # ---- inference, fused: 18 launches per network evaluation (csrc/denoise.hip)
     @torch.no_grad()
-    def build_fused(self, ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=True):
+    def build_fused(self, ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=True, n_cand=1):
         """Step-invariant state of the fused sampling path for one trajectory batch: the context K (fp16 hi | lo rows) / V (fp16
         hi / lo planes) of every cross-attention layer, the instruction tokens through traj_lang_attention's k | v projection, and
         the AdaLN modulation of every layer at every row of time_sin (Linear(SiLU(sinusoidal(t))), layers.py:273-290): all T timesteps
         for the full chain, only the K scheduled ones -- in step order -- under a SamplerSchedule.  Returns
-        {"tensors": [...]} -- the list is what a captured graph must refresh in place -- plus per-layer pointer tables."""
+        {"tensors": [...]} -- the list is what a captured graph must refresh in place -- plus per-layer pointer tables.
+        n_cand > 1 (compute_trajectory(num_samples=...)): ctx / ctx_xyz / instr hold one sample per SCENE and every cache tensor keeps
+        that leading dimension B; kmask and the persistent sampler's workspaces are per trajectory, B * n_cand of them
+        (a3d_dn_persist_group); the per-phase workspaces (ws) are not for such a state."""
         B, S, E = ctx.shape
         H = self.num_attn_heads
         dev = ctx.device
@@ -442,7 +461,7 @@ class DiffusionHead(nn.Module):
         f4 = 4
         freq = O.rope_freq(E, dev)
         silu = F.silu(time_sin)                                         # (T, E)
-        st = {"S": S, "Sp": Sp, "layers": [], "tensors": [], "freq": freq, "sem": self._sem(Ln, E, dev), "kmask": kmask}
+        st = {"S": S, "Sp": Sp, "layers": [], "tensors": [], "freq": freq, "sem": self._sem(Ln, E, dev), "kmask": kmask, "n_cand": n_cand}
         ctx = O._c(ctx)
         xyz = O._c(ctx_xyz.float())
         for lay in self._cross_layers():
@@ -471,20 +490,26 @@ class DiffusionHead(nn.Module):
         st["ws_side"] = torch.empty((nws,), device=dev, dtype=torch.float32)      # rotation branch, concurrent
         # with_persist=False: the caller is about to replay a captured graph that owns its persistent-sampler state (tables, exchange
         # buffers, synchronisation words) -- only the refreshed K / V / modulation tensors of this call are needed
-        st["persist"] = self._build_persist(st, B, Ln, H, E, Sp, time_sin.shape[0], dev) if (DN_PERSIST and with_persist) else None
+        st["persist"] = self._build_persist(st, B * n_cand, Ln, H, E, Sp, time_sin.shape[0], dev) if (DN_PERSIST and with_persist) else None
         return st
+
+    def persist_fits(self, B, Ln, dev):
+        """Whether the persistent sampler can serve B trajectories of Ln steps: two sample-role workgroups per (trajectory, 16-step
+        row tile) -- primary + rotation-stack helper -- and >= 16 streamers, all co-resident."""
+        NT = -(-Ln // 16)
+        return not (2 * B * NT + 16 > torch.cuda.get_device_properties(dev).multi_processor_count or self.num_attn_heads > 8 or NT > 4)
 
     def _build_persist(self, st, B, Ln, H, E, Sp, T, dev):
         """State of the persistent sampler (a3d_dn_persist: the whole denoise loop as one launch, csrc/denoise.hip): the device
         table of per-layer parameter blocks (AdaLN tables by their base: the kernel indexes them with the step), the query /
         partial exchange buffers and the synchronisation words.  None when the batch leaves too few CUs for the streaming role.
+        B: TRAJECTORIES (scenes x st["n_cand"] candidates: the workspaces are per trajectory, the K / V tables of st per scene).
         T: rows of the AdaLN tables -- the training timesteps, or the K steps of a sampler schedule (a3d_dn_persist_sched)."""
         import ctypes
         Lb = O.L
         lib = Lb.load()
         NT = -(-Ln // 16)                                   # 16-step row tiles per trajectory: one sample-role workgroup each
-        # two sample-role workgroups per (trajectory, tile) -- primary + rotation-stack helper -- and >= 16 streamers, all co-resident
-        if 2 * B * NT + 16 > torch.cuda.get_device_properties(dev).multi_processor_count or H > 8 or NT > 4:
+        if not self.persist_fits(B, Ln, dev):
             return None
         recs = st["layers"]
         table = (Lb.DnLayerParams * len(recs))()
@@ -516,6 +541,8 @@ class DiffusionHead(nn.Module):
             "sync": torch.zeros((lib.a3d_dn_persist_sync_ints(B, Ln, n_layers, T),), device=dev, dtype=torch.int32),
             "stacks": (len(self.traj_attention[0].layers), len(self.pos_attention[0].layers), len(self.rot_attention[0].layers)),
             "rows": T,                                          # rows of the AdaLN tables = the most steps one launch may run
+            "n_cand": st.get("n_cand", 1),                      # candidates per scene: > 1 or a num_samples call -> a3d_dn_persist_group
+            "group": False,
         }
 
     @torch.no_grad()
@@ -523,7 +550,9 @@ class DiffusionHead(nn.Module):
         """nsteps consecutive denoise steps t_first, t_first - 1, ... (network evaluation + DDPM reverse step each) as ONE launch of
         the persistent sampler; returns the trajectory after the last of them (a new tensor).  step_noise: the (T, B, L, D) table.
         sched (a SamplerSchedule; st built on its timesteps): the steps at POSITIONS t_first, t_first + 1, ... of the schedule
-        (a3d_dn_persist_sched); step_noise is then (K, B, L, D) by position, or None for a noise-free schedule."""
+        (a3d_dn_persist_sched); step_noise is then (K, B, L, D) by position, or None for a noise-free schedule.
+        A state marked for candidate groups (ps["group"]: compute_trajectory(num_samples=G), always on a schedule) goes through
+        a3d_dn_persist_group: traj holds scenes x n_cand trajectories, scene-major, against the per-scene cache of st."""
         Lb = O.L
         ps = st["persist"]
         B, Ln, D = traj.shape
@@ -553,11 +582,17 @@ class DiffusionHead(nn.Module):
                   B, Ln, D, E, H, st["S"], st["Sp"], ps["nsplit"], int(t_first), int(nsteps))
         if sched is None:
             entry = "a3d_dn_persist"
+            assert not ps["group"]
             Lb.call(entry, *common, Lb.stream())
         else:
-            entry = "a3d_dn_persist_sched"
             assert tb is sched and ps["rows"] == sched.K and (step_noise is None) == sched.noise_free
-            Lb.call(entry, *common, sched.K, int(t_first + nsteps == sched.K), Lb.stream())
+            if ps["group"]:
+                entry = "a3d_dn_persist_group"
+                assert B % ps["n_cand"] == 0 and st["layers"][0]["Kf"].shape[0] * ps["n_cand"] == B
+                Lb.call(entry, *common, sched.K, int(t_first + nsteps == sched.K), ps["n_cand"], Lb.stream())
+            else:
+                entry = "a3d_dn_persist_sched"
+                Lb.call(entry, *common, sched.K, int(t_first + nsteps == sched.K), Lb.stream())
         if DN_PERSIST_CHECK:
             if int(ps["sync"][2].item()) != 0:
                 raise RuntimeError(entry + " gave up waiting (sync[2] != 0): the trajectory is invalid")
@@ -792,15 +827,22 @@ class DiffusionPlanner(nn.Module):
     @torch.no_grad()
     def compute_trajectory(self, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, *,
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
-                           return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0):
+                           return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
         i used by the i-th executed step, and is neither drawn nor read for "ddim" with eta = 0.  n_steps truncates the (scheduled)
-        step list for fixtures; a truncated run has no terminal step."""
+        step list for fixtures; a truncated run has no terminal step.
+        num_samples = G (an integer >= 1) draws G candidate trajectories per scene and returns (B, G, L, 8) (trace entries
+        (B, G, L, D)): init_noise is then (B, G, L, D) and step_noise (steps, B, G, L, D); every other input stays per scene.  The
+        step-invariant setup (encoding, K / V cache, instruction rows) runs once per scene and the persistent sampler streams a
+        scene's cache once for a chunk of candidates (a3d_dn_persist_group); trajectory b G + g belongs to scene b.  Where that
+        kernel cannot serve the call (A3D_DN_PERSIST=0, too many trajectories for the CU count, multi-round heads, fused=False)
+        the context is expanded along the batch axis and the call runs on the single-candidate paths."""
         head = self.prediction_head
         dev = pcd_obs.device
         B, Ln = trajectory_mask.shape
+        G = None if num_samples is None else check_num_samples(num_samples)
         # host-side checks first: bad schedule arguments raise before anything is launched
         scheduled = num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0
         if scheduled:
@@ -808,10 +850,39 @@ class DiffusionPlanner(nn.Module):
             if step_noise is not None and step_noise.shape[0] != K:
                 raise ValueError("step_noise has %d leading rows for a schedule of %d steps (one row per step position)"
                                  % (step_noise.shape[0], K))
+        if G is not None:
+            check_candidate_noise(init_noise, step_noise, B, G, Ln, curr_gripper.shape[-1] + 2, K if scheduled else self.n_steps)
+        multi = head.attn_rounds * head.feat_scales > 1
         tb = self.tables(dev)
+        # candidate groups: the persistent sampler on the per-scene cache.  Decided on the host from the shapes alone, by the
+        # conditions that select the fused path and the persistent sampler below.
+        E_ = head.curr_gripper_embed.weight.shape[1]
+        D_ = curr_gripper.shape[-1] + 2
+        group = (G is not None and not multi and (FUSED_DENOISE if fused is None else fused) and DN_PERSIST and E_ <= 128 and
+                 D_ <= 16 and min(Ln, 16) * D_ <= 160 and Ln <= 64 and head.persist_fits(B * G, Ln, dev))
+        flip_noise = False
+        if group and not scheduled:
+            # a3d_dn_persist_group addresses its tables by step position: the full chain is the K = T "ddpm" schedule (the same
+            # coefficients and AdaLN rows, bit for bit), with the noise of timestep t at row T - 1 - t
+            scheduled, K, flip_noise = True, self.n_steps, True
         sched = self.schedule(dev, K, scheduler, eta) if scheduled else None
         tokens, ctx_xyz, cg, gg = self._prepare(rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens)
-        multi = head.attn_rounds * head.feat_scales > 1
+        B_scene = B
+        if G is not None:
+            rows = self.n_steps if (sched is None or flip_noise) else sched.K
+            if init_noise is not None:
+                init_noise = init_noise.reshape(B * G, Ln, -1)
+            if step_noise is not None:
+                step_noise = step_noise.reshape(rows, B * G, Ln, -1)
+                if flip_noise:
+                    step_noise = step_noise.flip(0)
+            if not group:
+                # fallback paths: every scene's inputs G times along the batch axis (after the image encoding, which stays per scene)
+                rep_ = lambda x: None if x is None else x.repeat_interleave(G, 0)
+                tokens = [rep_(x) for x in tokens] if isinstance(tokens, (list, tuple)) else rep_(tokens)
+                ctx_xyz = [rep_(x) for x in ctx_xyz] if isinstance(ctx_xyz, (list, tuple)) else rep_(ctx_xyz)
+                cg, gg, instruction, trajectory_mask = rep_(cg), rep_(gg), rep_(instruction), rep_(trajectory_mask)
+                B = B * G
         if not multi:
             ctx, ctx_xyz, instr = head.encode_context(tokens, ctx_xyz, instruction, cg, gg)
         # conditioning: start pose at index 0, goal at L - pad - 1 and after (no host sync: index arithmetic on device)
@@ -827,6 +898,11 @@ class DiffusionPlanner(nn.Module):
             cond_data = torch.where((ar == gidx)[..., None], gg[:, None, :], cond_data)
         cond_mask_u8 = cond_mask[..., None].expand(B, Ln, D).to(torch.uint8).contiguous()
         cond_data = cond_data.contiguous()
+        kmask = trajectory_mask.to(torch.uint8).contiguous()
+        if group:
+            # per trajectory from here on: conditioning, masks, noise, the trajectory itself (scene-major); ctx / instr stay per scene
+            cond_mask_u8, cond_data, kmask = (x.repeat_interleave(G, 0).contiguous() for x in (cond_mask_u8, cond_data, kmask))
+            B = B * G
         if init_noise is None:
             init_noise = torch.randn((B, Ln, D), device=dev)
         if sched is not None and sched.noise_free:
@@ -841,8 +917,9 @@ class DiffusionPlanner(nn.Module):
         # tables of the DDPM-step kernels and of the AdaLN modulation: by timestep (full chain) or by step position (schedule)
         time_sin = self._time_tables["sin"] if sched is None else sched.time_sin
         sched_key = None if sched is None else sched.key
+        if G is not None:
+            sched_key = (sched_key, "num_samples", G, "group" if group else "expanded")
         traj = (init_noise.to(dev).float() + cond_data).contiguous()
-        kmask = trajectory_mask.to(torch.uint8).contiguous()
         trace = []
         # fused per-step kernels (csrc/denoise.hip) whenever the trajectory fits one 16-row tile; else the op-by-op path
         fused = FUSED_DENOISE if fused is None else fused
@@ -862,9 +939,11 @@ class DiffusionPlanner(nn.Module):
             gr_ = self._graph
             reuse = (use_graph and not return_trace and gr_ is not None and gr_["key"][:3] == (B, Ln, tuple(steps)) and
                      gr_["key"][-1] == sched_key and isinstance(gr_.get("state"), dict) and gr_["state"].get("persist") is not None)
-            state = head.build_fused(ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=not reuse)
+            state = head.build_fused(ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=not reuse, n_cand=G if group else 1)
             if reuse:
                 state["persist"] = gr_["state"]["persist"]
+            elif group and state["persist"] is not None:
+                state["persist"]["group"] = True
             static = list(state["tensors"])
             if Ln > 16 and state.get("persist") is None:           # too many units for the CU count: the op-by-op path serves it
                 fused = False
@@ -882,9 +961,14 @@ class DiffusionPlanner(nn.Module):
         # the persistent sampler walks its tables row by row: consecutive timesteps of the full chain, or any schedule by position
         in_order = sched is not None or all(a_ - b_ == 1 for a_, b_ in zip(steps, steps[1:]))
         persist = fused and state.get("persist") is not None and in_order
+        if group and not persist:
+            raise RuntimeError("num_samples: the per-scene cache was built for a3d_dn_persist_group, which cannot serve this call")
+        if G is not None:
+            self._last_state = state                        # tests read the leading dimensions of the cache
         # which sampler serves this call (read by the bench line and the tests)
         self.last_sampler_path = "multi-round" if multi else (
-            ("persistent (a3d_dn_persist)" if sched is None else "persistent (a3d_dn_persist_sched)") if persist else
+            ("persistent (a3d_dn_persist_group)" if group else
+             "persistent (a3d_dn_persist)" if sched is None else "persistent (a3d_dn_persist_sched)") if persist else
             ("per-phase fused launches" if fused else "op-by-op"))
 
         def run_scheduled(x):
@@ -936,6 +1020,8 @@ class DiffusionPlanner(nn.Module):
             if self._graph is not None and self._graph["key"] != key and fused and state.get("persist") is self._graph["state"].get("persist"):
                 # the shapes changed after all (another context size): this call needs its own persistent-sampler state
                 state["persist"] = head._build_persist(state, B, Ln, head.num_attn_heads, E, state["Sp"], time_sin.shape[0], dev) if DN_PERSIST else None
+                if group and state["persist"] is not None:
+                    state["persist"]["group"] = True
                 persist = fused and state.get("persist") is not None and in_order
             if self._graph is None or self._graph["key"] != key:
                 static_in = traj.clone()
@@ -961,4 +1047,7 @@ class DiffusionPlanner(nn.Module):
         else:
             traj = run_loop(traj)
         final = signal_to_pose(traj, self.gripper_loc_bounds)
+        if G is not None:
+            final = final.reshape(B_scene, G, Ln, final.shape[-1])
+            trace = [x.reshape(B_scene, G, Ln, x.shape[-1]) for x in trace]
         return (final, trace) if return_trace else final

@@ -489,6 +489,22 @@ int a3d_dn_persist_sched(const a3d_dn_layer_params* layers_dev, int n_traj, int 
                          const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
                          int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int row_first, int nsteps, int n_rows,
                          int last_terminal, void* stream);
+/* a3d_dn_persist_sched for several candidate trajectories per scene that share the scene's context: B counts TRAJECTORIES, B % n_cand
+ * == 0, scene-major -- trajectory j = scene * n_cand + candidate belongs to scene j / n_cand.  Everything context-sized has B / n_cand
+ * samples and is indexed by scene: cross.Kf / cross.Vt of every layer and head->lang_kv (built ONCE per scene).  Everything else is
+ * per trajectory and sized for B as above: traj, tail->noise ([n_rows][B][L][D]), tail->cond_data / cond_mask, rest.kmask, qbuf,
+ * part, kvx, xbuf, sync.  One streaming item serves a CHUNK of max(1, 4 / NT) consecutive candidates of a scene (at most four 16-row
+ * tiles; a scene's last chunk may be smaller): the scene's K / V slice is read once for all of them.  The candidates are independent
+ * trajectories (no self-attention exchange between them; each starts at row 0 of the step-index embedding).  n_cand = 1 is
+ * a3d_dn_persist_sched.  Same co-residency limit, 2 * B * NT + 16 <= the device's CU count with B the trajectory count; otherwise
+ * A3D_ERR_ARG -> per-phase entry points on a context expanded to B samples, or fewer trajectories per call.  sync[2] as above. */
+/* host-only mirror of that grouping, for tests: trajectory `traj` (< B = scenes * n_cand) -> out5 = {groups per role, the trajectory's
+ * group within a role (scene * chunks per scene + chunk), the group's first unit (trajectory * NT + tile), its tile count, the scene} */
+int a3d_dn_persist_group_of(int B, int L, int n_cand, int traj, int* out5);
+int a3d_dn_persist_group(const a3d_dn_layer_params* layers_dev, int n_traj, int n_pos, int n_rot, const a3d_dn_head_params* head,
+                         const a3d_dn_tail_params* tail, float* traj, float* qbuf, float* part, float* kvx, float* xbuf, int* sync,
+                         int B, int L, int D, int E, int H, int S, int Sp, int nsplit, int row_first, int nsteps, int n_rows,
+                         int last_terminal, int n_cand, void* stream);
 /* development aid: 18 phase timestamps (100 MHz ticks) of workgroup 0 of the last a3d_dn_rest launch under A3D_DN_PROF=1 (host buffer) */
 int a3d_dbg_dn_prof(long long* out18);
 /* out[b][h][n][16] fp32 = rope3d(Y[b, n, :E] * scale, xyz) split into heads (column 15 and rows >= N zero): the K cache */
