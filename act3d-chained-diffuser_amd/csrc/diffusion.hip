@@ -181,33 +181,81 @@ __global__ void traj_update_kernel(const float* __restrict__ traj, const float* 
 // written from the closed forms: R(q) for a unit quaternion (w, x, y, z); 6D = the first two columns of R; back:
 // Gram-Schmidt of the two 3-vectors, then the quaternion from the best-conditioned of the four trace identities.
 // One thread per pose row; rows carry `extra` trailing channels that pass through.
+// pose_row_to_signal is the row map itself, shared with traj_condition_kernel so that both produce the same bits.
+__device__ __forceinline__ void pose_row_to_signal(const float* __restrict__ r, const float* __restrict__ bounds,
+                                                   float* __restrict__ o, int extra) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (bounds) {
+      const float lo = bounds[a], hi = bounds[3 + a];
+      o[a] = (r[a] - lo) / (hi - lo) * 2.0f - 1.0f;
+    } else {
+      o[a] = r[a];
+    }
+  }
+  float w = r[3], x = r[4], y = r[5], z = r[6];
+  const float nrm = fmaxf(sqrtf(w * w + x * x + y * y + z * z), 1e-10f);
+  w /= nrm; x /= nrm; y /= nrm; z /= nrm;
+  const float t = 2.0f / (w * w + x * x + y * y + z * z);
+  // first column of R, then the second
+  o[3] = 1.0f - t * (y * y + z * z);
+  o[4] = t * (x * y + z * w);
+  o[5] = t * (x * z - y * w);
+  o[6] = t * (x * y - z * w);
+  o[7] = 1.0f - t * (x * x + z * z);
+  o[8] = t * (y * z + x * w);
+  for (int e = 0; e < extra; ++e) o[9 + e] = r[7 + e];
+}
+
 __global__ void pose_to_signal_kernel(const float* __restrict__ in, const float* __restrict__ bounds,
                                       float* __restrict__ out, int n, int extra) {
   const int Din = 7 + extra, Dout = 9 + extra;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float* r = in + (size_t)i * Din;
-    float* o = out + (size_t)i * Dout;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      if (bounds) {
-        const float lo = bounds[a], hi = bounds[3 + a];
-        o[a] = (r[a] - lo) / (hi - lo) * 2.0f - 1.0f;
-      } else {
-        o[a] = r[a];
-      }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    pose_row_to_signal(in + (size_t)i * Din, bounds, out + (size_t)i * Dout, extra);
+}
+
+// ---------------------------------------------------------------- conditioning of a sampling call in one launch
+// diffusion_model.py:131-168: the start / goal poses as network signals, the in-painting data and mask (start pose on row 0, goal
+// pose on row L - pad - 1 and the mask from there on, pad = the number of padded steps of the scene) and the noisy start
+// trajectory.  One workgroup row per scene (blockIdx.x = b); its G trajectories b G + g are spread over blockIdx.y.  Every
+// workgroup converts the scene's two poses and counts its padding itself (a few hundred flops), so there is no second launch
+// and nothing is exchanged through memory.
+constexpr int TC_MAX_D = 32;                                      // signal channels a workgroup keeps in LDS (D = Dp + 2)
+__global__ __launch_bounds__(256) void traj_condition_kernel(
+    const float* __restrict__ curr, int ldc, const float* __restrict__ goal, int ldg, const float* __restrict__ bounds,
+    const unsigned char* __restrict__ tmask, const float* __restrict__ init_noise, float* __restrict__ cg,
+    float* __restrict__ gg, float* __restrict__ cond_data, unsigned char* __restrict__ cond_mask,
+    unsigned char* __restrict__ kmask, float* __restrict__ traj, int G, int L, int Dp, int use_goal) {
+  __shared__ float s_sig[2][TC_MAX_D];
+  __shared__ int s_cnt[256];
+  const int b = blockIdx.x, t = threadIdx.x, D = Dp + 2;
+  const unsigned char* mrow = tmask + (size_t)b * L;
+  if (t < 2) pose_row_to_signal(t == 0 ? curr + (size_t)b * ldc : goal + (size_t)b * ldg, bounds, s_sig[t], Dp - 7);
+  int cnt = 0;
+  for (int l = t; l < L; l += 256) cnt += mrow[l] != 0;
+  s_cnt[t] = cnt;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) s_cnt[t] += s_cnt[t + s];
+    __syncthreads();
+  }
+  const int gidx = L - s_cnt[0] - 1;                              // -1: the whole row is padding -- all masked, no goal row
+  if (blockIdx.y == 0 && t < 2 * D) {
+    if (t < D) cg[(size_t)b * D + t] = s_sig[0][t];
+    else gg[(size_t)b * D + (t - D)] = s_sig[1][t - D];
+  }
+  const int LD = L * D;
+  for (int g = blockIdx.y; g < G; g += gridDim.y) {
+    const size_t row = (size_t)b * G + g;
+    for (int i = t; i < LD; i += 256) {
+      const int l = i / D, c = i - l * D;
+      const float v = (use_goal && l == gidx) ? s_sig[1][c] : (l == 0 ? s_sig[0][c] : 0.0f);
+      const size_t j = row * LD + i;
+      cond_data[j] = v;
+      cond_mask[j] = (l == 0 || (use_goal && l >= gidx)) ? 1 : 0;
+      if (traj) traj[j] = init_noise[j] + v;
     }
-    float w = r[3], x = r[4], y = r[5], z = r[6];
-    const float nrm = fmaxf(sqrtf(w * w + x * x + y * y + z * z), 1e-10f);
-    w /= nrm; x /= nrm; y /= nrm; z /= nrm;
-    const float t = 2.0f / (w * w + x * x + y * y + z * z);
-    // first column of R, then the second
-    o[3] = 1.0f - t * (y * y + z * z);
-    o[4] = t * (x * y + z * w);
-    o[5] = t * (x * z - y * w);
-    o[6] = t * (x * y - z * w);
-    o[7] = 1.0f - t * (x * x + z * z);
-    o[8] = t * (y * z + x * w);
-    for (int e = 0; e < extra; ++e) o[9 + e] = r[7 + e];
+    for (int l = t; l < L; l += 256) kmask[row * L + l] = mrow[l] != 0 ? 1 : 0;
   }
 }
 
@@ -385,6 +433,24 @@ extern "C" int a3d_signal_to_pose(const float* signal, const float* bounds, floa
   if (!signal || !out || n <= 0 || extra < 0) { set_error("a3d_signal_to_pose: bad argument"); return A3D_ERR_ARG; }
   hipLaunchKernelGGL(signal_to_pose_kernel, dim3(gsz((size_t)n)), dim3(256), 0, (hipStream_t)stream, signal, bounds, out, n, extra);
   return check_launch("a3d_signal_to_pose");
+}
+extern "C" int a3d_traj_condition(const float* curr, int ldc, const float* goal, int ldg, const float* bounds,
+                                  const unsigned char* tmask, const float* init_noise, float* cg, float* gg, float* cond_data,
+                                  unsigned char* cond_mask, unsigned char* kmask, float* traj, int B, int G, int L, int Dp,
+                                  int use_goal, void* stream) {
+  if (!curr || !goal || !bounds || !tmask || !cg || !gg || !cond_data || !cond_mask || !kmask) {
+    set_error("a3d_traj_condition: null pointer"); return A3D_ERR_ARG;
+  }
+  if ((init_noise == nullptr) != (traj == nullptr)) {
+    set_error("a3d_traj_condition: init_noise and traj go together (both or neither)"); return A3D_ERR_ARG;
+  }
+  if (B <= 0 || G <= 0 || L <= 0) { set_error("a3d_traj_condition: B, G and L must be positive"); return A3D_ERR_ARG; }
+  if (Dp < 7 || Dp + 2 > a3d::TC_MAX_D) { set_error("a3d_traj_condition: Dp must lie in [7, 30]"); return A3D_ERR_ARG; }
+  if (ldc < Dp || ldg < Dp) { set_error("a3d_traj_condition: a leading dimension is smaller than Dp"); return A3D_ERR_ARG; }
+  if ((long long)L * (Dp + 2) > 0x7fffffffLL) { set_error("a3d_traj_condition: L * D overflows int"); return A3D_ERR_ARG; }
+  hipLaunchKernelGGL(traj_condition_kernel, dim3(B, G < 64 ? G : 64), dim3(256), 0, (hipStream_t)stream, curr, ldc, goal, ldg,
+                     bounds, tmask, init_noise, cg, gg, cond_data, cond_mask, kmask, traj, G, L, Dp, use_goal ? 1 : 0);
+  return check_launch("a3d_traj_condition");
 }
 extern "C" int a3d_traj_errors(const float* pred, const float* gt, float* cols, int B, int L, int D, void* stream) {
   if (!pred || !gt || !cols || B <= 0 || L <= 0 || D < 7) { set_error("a3d_traj_errors: bad argument (B=%d L=%d D=%d, D >= 7)", B, L, D); return A3D_ERR_ARG; }

@@ -15,7 +15,8 @@ What is restructured, with identical results:
 The DDPM schedules restate diffusers' DDPMScheduler (third-party, un-pinned -> parity unpinned).
 Additive keyword arguments: `noise`, `timesteps` (training) and `init_noise`, `step_noise` (sampling) inject the random
 draws; `visual_tokens` bypasses the backbone + FPN; `num_inference_steps` / `scheduler` / `eta` select a few-step sampler
-schedule; `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8).  Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
+schedule; `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8);
+`fused_conditioning=True` builds the sampler's conditioning tensors in one launch (a3d_traj_condition).  Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
 attention weights, residual branches, FFN -- and in the traj_encoder / regressor MLPs: layers.py:10,
 diffusion_head.py:46,183,193) runs on a device-resident Philox stream (csrc/dropout.hip, attention kernels): same
 distribution as the reference's torch generator, not the same draws.  The additive constructor keyword `dropout`
@@ -162,6 +163,54 @@ def signal_to_pose(signal, bounds=None):
     O.L.call("a3d_signal_to_pose", x.data_ptr(), None if bounds is None else bounds.data_ptr(), out.data_ptr(), n, D - 9,
              O.L.stream())
     return out
+
+
+def _pose_rows(x, name):
+    """(tensor, leading dimension in floats) of fp32 pose rows (B, Dp) the kernel can read in place: unit stride inside a row, any
+    row stride >= Dp (a slice of a wider tensor, e.g. action[..., :7] of (B, 8) rows); anything else is copied."""
+    if x.dim() != 2:
+        raise ValueError("%s must be (B, Dp) pose rows, got shape %s" % (name, tuple(x.shape)))
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x, (x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1]))
+
+
+def traj_condition(curr_gripper, goal_gripper, bounds, trajectory_mask, init_noise=None, num_samples=1, use_goal=True):
+    """The conditioning of a sampling call in ONE launch (a3d_traj_condition, csrc/diffusion.hip; diffusion_model.py:131-168):
+    returns (cg, gg, cond_data, cond_mask_u8, kmask, traj) -- the two poses as signals (B, D) (bit-equal to pose_to_signal), the
+    in-painting data / mask (B G, L, D) and the key mask (B G, L) of G = num_samples trajectories per scene (scene-major), and
+    traj = init_noise + cond_data when init_noise (B G, L, D) is given (None otherwise).  curr_gripper / goal_gripper: (B, Dp)
+    rows, read in place where they are row slices of a wider tensor; trajectory_mask: (B, L), non-zero = padded step."""
+    cur, ldc = _pose_rows(curr_gripper, "curr_gripper")
+    goal, ldg = _pose_rows(goal_gripper, "goal_gripper")
+    B, Dp = cur.shape
+    G = int(num_samples)
+    if tuple(goal.shape) != (B, Dp):
+        raise ValueError("goal_gripper has shape %s, curr_gripper %s" % (tuple(goal.shape), (B, Dp)))
+    if trajectory_mask.dim() != 2 or trajectory_mask.shape[0] != B:
+        raise ValueError("trajectory_mask must be (B, L) with B = %d, got %s" % (B, tuple(trajectory_mask.shape)))
+    Ln, D = trajectory_mask.shape[1], Dp + 2
+    if init_noise is not None and tuple(init_noise.shape) != (B * G, Ln, D):
+        raise ValueError("init_noise has shape %s, the call needs %s" % (tuple(init_noise.shape), (B * G, Ln, D)))
+    O.L.require_gpu(cur, goal, bounds, trajectory_mask, init_noise)
+    tm = trajectory_mask.detach()
+    # a bool tensor stores 0 / 1 bytes: read in place
+    tm = O._c(tm).view(torch.uint8) if tm.dtype == torch.bool else O._c((tm != 0).view(torch.uint8) if tm.dtype != torch.uint8 else tm)
+    dev = cur.device
+    noise = None if init_noise is None else O._c(init_noise.detach().float())
+    cg = torch.empty((B, D), device=dev, dtype=torch.float32)
+    gg = torch.empty((B, D), device=dev, dtype=torch.float32)
+    cond_data = torch.empty((B * G, Ln, D), device=dev, dtype=torch.float32)
+    cond_mask = torch.empty((B * G, Ln, D), device=dev, dtype=torch.uint8)
+    kmask = torch.empty((B * G, Ln), device=dev, dtype=torch.uint8)
+    traj = None if noise is None else torch.empty((B * G, Ln, D), device=dev, dtype=torch.float32)
+    O.L.call("a3d_traj_condition", cur.data_ptr(), ldc, goal.data_ptr(), ldg, O._c(bounds).data_ptr(), tm.data_ptr(),
+             None if noise is None else noise.data_ptr(), cg.data_ptr(), gg.data_ptr(), cond_data.data_ptr(), cond_mask.data_ptr(),
+             kmask.data_ptr(), None if traj is None else traj.data_ptr(), B, G, Ln, Dp, 1 if use_goal else 0, O.L.stream())
+    return cg, gg, cond_data, cond_mask, kmask, traj
 
 
 # ------------------------------------------------------------------------------------------------ prediction head
@@ -772,9 +821,10 @@ class DiffusionPlanner(nn.Module):
     def unconvert_rot(self, signal):
         return signal_to_pose(signal)
 
-    def _prepare(self, rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens):
+    def _prepare(self, rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens, signals=True):
         """Normalised, converted conditioning + visual tokens and their (normalised, down-sampled) coordinates
-        (one tensor each, or one per scale for a multi-scale head)."""
+        (one tensor each, or one per scale for a multi-scale head).  signals=False: the caller converts the two poses itself
+        (traj_condition) -- cg and gg come back as None."""
         head = self.prediction_head
         with torch.no_grad():
             pcd_n = self.normalize_pos(pcd_obs.float().permute(0, 1, 3, 4, 2)).permute(0, 1, 4, 2, 3).contiguous()
@@ -783,8 +833,8 @@ class DiffusionPlanner(nn.Module):
                 if f not in by_factor:
                     by_factor[f] = O.pcd_downsample(pcd_n, f)
             ctx_xyz = [by_factor[f] for f in head.downscaling_factor_pyramid[:head.feat_scales]]
-            cg = pose_to_signal(curr_gripper, self.gripper_loc_bounds)
-            gg = pose_to_signal(goal_gripper, self.gripper_loc_bounds)
+            cg = pose_to_signal(curr_gripper, self.gripper_loc_bounds) if signals else None
+            gg = pose_to_signal(goal_gripper, self.gripper_loc_bounds) if signals else None
         tokens = visual_tokens if visual_tokens is not None else head.encode_images(rgb_obs, pcd_n)
         if head.feat_scales == 1:
             ctx_xyz = ctx_xyz[0]
@@ -827,7 +877,8 @@ class DiffusionPlanner(nn.Module):
     @torch.no_grad()
     def compute_trajectory(self, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, *,
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
-                           return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None):
+                           return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None,
+                           fused_conditioning=False):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
@@ -838,7 +889,10 @@ class DiffusionPlanner(nn.Module):
         step-invariant setup (encoding, K / V cache, instruction rows) runs once per scene and the persistent sampler streams a
         scene's cache once for a chunk of candidates (a3d_dn_persist_group); trajectory b G + g belongs to scene b.  Where that
         kernel cannot serve the call (A3D_DN_PERSIST=0, too many trajectories for the CU count, multi-round heads, fused=False)
-        the context is expanded along the batch axis and the call runs on the single-candidate paths."""
+        the context is expanded along the batch axis and the call runs on the single-candidate paths.
+        fused_conditioning=True: the two pose conversions, the in-painting data / mask, the key mask and the noisy start trajectory
+        come from ONE launch (traj_condition) instead of ~25 small ones, per trajectory of a multi-candidate call included; the
+        result is the same, bit for bit."""
         head = self.prediction_head
         dev = pcd_obs.device
         B, Ln = trajectory_mask.shape
@@ -866,7 +920,17 @@ class DiffusionPlanner(nn.Module):
             # coefficients and AdaLN rows, bit for bit), with the noise of timestep t at row T - 1 - t
             scheduled, K, flip_noise = True, self.n_steps, True
         sched = self.schedule(dev, K, scheduler, eta) if scheduled else None
-        tokens, ctx_xyz, cg, gg = self._prepare(rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens)
+        tokens, ctx_xyz, cg, gg = self._prepare(rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens,
+                                                signals=not fused_conditioning)
+        if fused_conditioning:
+            # every per-trajectory conditioning tensor at once, before the candidate expansion below (the kernel expands itself)
+            Gk = 1 if G is None else G
+            if init_noise is None:
+                init_noise = torch.randn((B * Gk, Ln, D_), device=dev)
+            else:
+                init_noise = init_noise.to(dev).float().reshape(B * Gk, Ln, -1)
+            cg, gg, cond_data, cond_mask_u8, kmask, traj = traj_condition(
+                curr_gripper, goal_gripper, self.gripper_loc_bounds, trajectory_mask, init_noise, Gk, self._use_goal_at_test)
         B_scene = B
         if G is not None:
             rows = self.n_steps if (sched is None or flip_noise) else sched.K
@@ -888,20 +952,22 @@ class DiffusionPlanner(nn.Module):
         # conditioning: start pose at index 0, goal at L - pad - 1 and after (no host sync: index arithmetic on device)
         D = cg.shape[-1]
         E = head.curr_gripper_embed.weight.shape[1]
-        ar = torch.arange(Ln, device=dev)[None, :]
-        cond_mask = (ar == 0)
-        cond_data = torch.zeros((B, Ln, D), device=dev)
-        cond_data[:, 0] = cg
-        if self._use_goal_at_test:
-            gidx = (Ln - trajectory_mask.sum(1).long() - 1)[:, None]
-            cond_mask = cond_mask | (ar >= gidx)
-            cond_data = torch.where((ar == gidx)[..., None], gg[:, None, :], cond_data)
-        cond_mask_u8 = cond_mask[..., None].expand(B, Ln, D).to(torch.uint8).contiguous()
-        cond_data = cond_data.contiguous()
-        kmask = trajectory_mask.to(torch.uint8).contiguous()
+        if not fused_conditioning:
+            ar = torch.arange(Ln, device=dev)[None, :]
+            cond_mask = (ar == 0)
+            cond_data = torch.zeros((B, Ln, D), device=dev)
+            cond_data[:, 0] = cg
+            if self._use_goal_at_test:
+                gidx = (Ln - trajectory_mask.sum(1).long() - 1)[:, None]
+                cond_mask = cond_mask | (ar >= gidx)
+                cond_data = torch.where((ar == gidx)[..., None], gg[:, None, :], cond_data)
+            cond_mask_u8 = cond_mask[..., None].expand(B, Ln, D).to(torch.uint8).contiguous()
+            cond_data = cond_data.contiguous()
+            kmask = trajectory_mask.to(torch.uint8).contiguous()
         if group:
             # per trajectory from here on: conditioning, masks, noise, the trajectory itself (scene-major); ctx / instr stay per scene
-            cond_mask_u8, cond_data, kmask = (x.repeat_interleave(G, 0).contiguous() for x in (cond_mask_u8, cond_data, kmask))
+            if not fused_conditioning:
+                cond_mask_u8, cond_data, kmask = (x.repeat_interleave(G, 0).contiguous() for x in (cond_mask_u8, cond_data, kmask))
             B = B * G
         if init_noise is None:
             init_noise = torch.randn((B, Ln, D), device=dev)
@@ -919,7 +985,10 @@ class DiffusionPlanner(nn.Module):
         sched_key = None if sched is None else sched.key
         if G is not None:
             sched_key = (sched_key, "num_samples", G, "group" if group else "expanded")
-        traj = (init_noise.to(dev).float() + cond_data).contiguous()
+        if fused_conditioning:
+            sched_key = (sched_key, "fused_conditioning")
+        else:
+            traj = (init_noise.to(dev).float() + cond_data).contiguous()
         trace = []
         # fused per-step kernels (csrc/denoise.hip) whenever the trajectory fits one 16-row tile; else the op-by-op path
         fused = FUSED_DENOISE if fused is None else fused

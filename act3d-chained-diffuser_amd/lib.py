@@ -75,6 +75,7 @@ SIGNATURES = {
     "a3d_attn16_bwd": (_i, [_p] * 16 + [_i] * 7 + [_p, C.c_uint, _f, _p]),
     "a3d_pose_to_signal": (_i, [_p, _p, _p, _i, _i, _p]),
     "a3d_signal_to_pose": (_i, [_p, _p, _p, _i, _i, _p]),
+    "a3d_traj_condition": (_i, [_p, _i, _p, _i, _p] + [_p] * 8 + [_i] * 5 + [_p]),
     "a3d_traj_errors": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "a3d_keypose_errors": (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
     "a3d_sym_quat_loss": (_i, [_p, _p, _i, _f, _p, _p, _i, _p]),

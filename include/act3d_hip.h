@@ -389,6 +389,19 @@ int a3d_traj_update(const float* traj, const float* upd, float* out, int rows, i
  * Gram-Schmidt of the 6D part, quaternion from the best-conditioned trace identity. */
 int a3d_pose_to_signal(const float* pose, const float* bounds, float* out, int n, int extra, void* stream);
 int a3d_signal_to_pose(const float* signal, const float* bounds, float* out, int n, int extra, void* stream);
+/* The conditioning of one sampling call in one launch (diffusion_model.py:131-168): B scenes, G trajectories per scene, rows
+ * scene-major (trajectory b G + g reads scene b).  curr / goal: pose rows [xyz | quat (w, x, y, z) | extra..] of Dp >= 7 channels
+ * with leading dimensions ldc / ldg >= Dp floats (goal may be the first Dp = 7 channels of (B, 8) action rows); bounds: device
+ * [2][3]; tmask: [B][L] bytes, non-zero = padded step.  D = Dp + 2 <= 32.  Writes
+ *   cg, gg     [B][D]       the poses as network signals, bit-equal to a3d_pose_to_signal
+ *   cond_data  [B G][L][D]  cg on row 0; with use_goal gg on row gidx = L - pad - 1 (pad = non-zero entries of the scene's mask
+ *                           row; gg wins on row 0; no goal row when gidx = -1); zero elsewhere
+ *   cond_mask  [B G][L][D]  bytes: 1 on row 0 and, with use_goal, on every row >= gidx
+ *   kmask      [B G][L]     bytes: the scene's mask row, 0 / 1
+ *   traj       [B G][L][D]  init_noise + cond_data (one fp32 add); init_noise and traj are both NULL or both given. */
+int a3d_traj_condition(const float* curr, int ldc, const float* goal, int ldg, const float* bounds, const unsigned char* tmask,
+                       const float* init_noise, float* cg, float* gg, float* cond_data, unsigned char* cond_mask,
+                       unsigned char* kmask, float* traj, int B, int G, int L, int Dp, int use_goal, void* stream);
 /* cols[b][9] of TrajectoryCriterion.compute_metrics (main_trajectory.py:303-343), see diffusion.hip; pred, gt: [B][L][D], D >= 7. */
 int a3d_traj_errors(const float* pred, const float* gt, float* cols, int B, int L, int D, void* stream);
 /* cols[b][6 + nlev] of LossAndMetrics.compute_metrics (main_keypose.py:431-482), see heads.hip; pos: [nlev + 1][B][3] with
