@@ -11,13 +11,16 @@ calls written out by hand, with identical results:
   * `predict(use_graph=True)`: one captured graph for the keypose half, followed by the sampler's own captured loop.
 Additive: constructor keywords `share_backbone`, `fused_conditioning`; `set_instruction` (RLBench's TASK_TO_ID table is not
 needed: `load_episode` only picks the instruction); keyword-only arguments of `predict` (`use_graph`, `ghost_points` and the
-sampling options of compute_trajectory).  Nothing in `predict` copies from the device to the host.
+sampling options of compute_trajectory, `select` / `rot_weight` for the on-device choice among `num_samples` candidates included).
+Nothing in `predict` copies from the device to the host.
 """
 import random
 
 import torch
 
-_TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps")
+from .diffusion import RANK_MAX_CANDIDATES, check_num_samples, check_rot_weight, check_select
+
+_TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight")
 
 
 def _same_tensors(a, b):
@@ -83,6 +86,7 @@ class Actioner:
         self._instr_cache = None
         self._graph = None
         self.last_backbone_passes = 0
+        self.last_ranking = None
         if predict_keypose:
             keypose_model.eval()
         if predict_trajectory:
@@ -240,11 +244,24 @@ class Actioner:
         """rgbs (B, history, cameras, 3, H, W) in [-1, 1]; pcds alike; gripper (B, history, >= action_dim); gt_action
         (B, history, >= action_dim), read only with predict_keypose=False; trajectory_mask (B, L), needed with
         predict_trajectory=True.  Returns {"action": (B, 8) or gt_action[:, -1], "trajectory": compute_trajectory's result or None,
-        "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps) go to
-        compute_trajectory unchanged; ghost_points to Act3D; use_graph replays the keypose half and the sampling loop as graphs."""
+        "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps, select,
+        rot_weight) go to compute_trajectory unchanged; with select the candidates are ranked on the device, "trajectory" is the
+        selected one (B, L, 8) and self.last_ranking mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
+        and the sampling loop as graphs."""
         bad = [k for k in sample_kw if k not in _TRAJ_KW]
         if bad:
             raise TypeError("predict() got unexpected keyword arguments %s" % bad)
+        if sample_kw.get("select") is not None:
+            # the ranking's own argument errors, before the keypose half launches anything
+            if not self._predict_trajectory:
+                raise ValueError("select ranks sampled trajectories: it needs predict_trajectory=True")
+            if sample_kw.get("num_samples") is None:
+                raise ValueError("select ranks the candidates of a num_samples=G call: give num_samples")
+            if check_num_samples(sample_kw["num_samples"]) > RANK_MAX_CANDIDATES:
+                raise ValueError("select serves at most %d candidates per scene, num_samples is %d" % (
+                    RANK_MAX_CANDIDATES, sample_kw["num_samples"]))
+            check_select(sample_kw["select"], True, True)
+            check_rot_weight(sample_kw.get("rot_weight", 1.0))
         self._check(rgbs, pcds, gripper, gt_action, trajectory_mask, use_graph, ghost_points)
         share = self._sharing()
         output = {"action": None, "attention": {}}
@@ -273,6 +290,8 @@ class Actioner:
                 trajectory_mask, rgb, pcd, instr, curr, output["action"][..., :self._action_dim], visual_tokens=tokens,
                 use_graph=use_graph, fused_conditioning=self._fused_conditioning, **sample_kw)
             passes += 0 if tokens is not None else 1
+            if sample_kw.get("select") is not None:
+                self.last_ranking = self._traj_model.last_ranking
         else:
             output["trajectory"] = None
         self.last_backbone_passes = passes

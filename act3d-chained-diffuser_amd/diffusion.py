@@ -16,12 +16,14 @@ The DDPM schedules restate diffusers' DDPMScheduler (third-party, un-pinned -> p
 Additive keyword arguments: `noise`, `timesteps` (training) and `init_noise`, `step_noise` (sampling) inject the random
 draws; `visual_tokens` bypasses the backbone + FPN; `num_inference_steps` / `scheduler` / `eta` select a few-step sampler
 schedule; `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8);
-`fused_conditioning=True` builds the sampler's conditioning tensors in one launch (a3d_traj_condition).  Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
+`fused_conditioning=True` builds the sampler's conditioning tensors in one launch (a3d_traj_condition); `select` / `rot_weight`
+rank the candidates on the device and return the selected trajectory (rank_trajectories, a3d_traj_rank).  Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
 attention weights, residual branches, FFN -- and in the traj_encoder / regressor MLPs: layers.py:10,
 diffusion_head.py:46,183,193) runs on a device-resident Philox stream (csrc/dropout.hip, attention kernels): same
 distribution as the reference's torch generator, not the same draws.  The additive constructor keyword `dropout`
 (default 0.1 = the reference) sets that probability; 0.0 disables it.
 """
+import collections
 import math
 import os
 
@@ -211,6 +213,99 @@ def traj_condition(curr_gripper, goal_gripper, bounds, trajectory_mask, init_noi
              None if noise is None else noise.data_ptr(), cg.data_ptr(), gg.data_ptr(), cond_data.data_ptr(), cond_mask.data_ptr(),
              kmask.data_ptr(), None if traj is None else traj.data_ptr(), B, G, Ln, Dp, 1 if use_goal else 0, O.L.stream())
     return cg, gg, cond_data, cond_mask, kmask, traj
+
+
+# ------------------------------------------------------------------------------------------------ candidate ranking
+RANK_TERMS = ("consensus", "goal", "smooth", "length", "bounds")
+RANK_PRESETS = {"consensus": "consensus", "goal": "goal", "smooth": "smooth", "shortest": "length"}
+RANK_MAX_CANDIDATES = 64
+TrajectoryRanking = collections.namedtuple("TrajectoryRanking", ("best", "order", "scores", "terms", "selected"))
+# what compute_trajectory(select=...) keeps on the planner: the ranking and all candidates (B, G, L, 8)
+PlannerRanking = collections.namedtuple("PlannerRanking", TrajectoryRanking._fields + ("candidates",))
+
+
+def check_select(select, have_goal=True, have_bounds=True):
+    """Validates a `select` rule on the host and returns its five weights in RANK_TERMS order.  A preset name ("consensus", "goal",
+    "smooth", "shortest") puts weight 1 on one term; a dict maps a subset of RANK_TERMS to finite, non-negative weights, not all zero.
+    A non-zero goal / bounds weight needs a goal / bounds."""
+    if isinstance(select, str):
+        if select not in RANK_PRESETS:
+            raise ValueError("select=%r: the presets are %s (or a dict over %s)" % (select, sorted(RANK_PRESETS), list(RANK_TERMS)))
+        select = {RANK_PRESETS[select]: 1.0}
+    elif not isinstance(select, dict):
+        raise ValueError("select must be a preset name or a dict of term weights, got %r" % (select,))
+    bad = [k for k in select if k not in RANK_TERMS]
+    if bad:
+        raise ValueError("select has unknown terms %s; the terms are %s" % (bad, list(RANK_TERMS)))
+    w = []
+    for k in RANK_TERMS:
+        v = select.get(k, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError("select[%r] = %r: a weight is a finite, non-negative number" % (k, v))
+        w.append(float(v))
+    if not any(w):
+        raise ValueError("select gives every term weight 0")
+    if w[1] != 0.0 and not have_goal:
+        raise ValueError("select weighs the goal term, but no goal is given")
+    if w[4] != 0.0 and not have_bounds:
+        raise ValueError("select weighs the bounds term, but no bounds are given")
+    return w
+
+
+def check_rot_weight(rot_weight):
+    if isinstance(rot_weight, bool) or not isinstance(rot_weight, (int, float)) or not math.isfinite(rot_weight) or rot_weight < 0:
+        raise ValueError("rot_weight must be a finite, non-negative number, got %r" % (rot_weight,))
+    return float(rot_weight)
+
+
+def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, select="consensus", rot_weight=1.0):
+    """Ranks the G candidate trajectories of every scene and selects one, in ONE launch (a3d_traj_rank, csrc/traj_rank.hip); nothing
+    is copied to the host.  trajectories: (B, G, L, Dp) fp32 poses [xyz | quaternion | opening], Dp = 7 or 8, scene-major as
+    compute_trajectory(num_samples=G) returns them, G <= 64; trajectory_mask: (B, L), non-zero = padded row (any pattern); goal:
+    (B, >= 7) pose rows, read in place where they are row slices of a wider tensor; bounds: (2, 3).
+    Terms per candidate over the valid rows: "consensus" (mean pose distance to all candidates of the scene: its argmin is the
+    medoid), "goal" (pose distance of the last valid row to the goal), "smooth" (mean squared second difference of the positions),
+    "length" (path length), "bounds" (share of rows outside the bounds); pose distance = position L2 + rot_weight (1 - <q, r>^2).
+    rot_weight = 1.0 is a choice, not a derived value: it prices a half turn (rho = 1) like one metre.  select: a preset name or a
+    dict of term weights (check_select).  Returns TrajectoryRanking(best (B,) int32, order (B, G) int32 ascending and stable,
+    scores (B, G), terms (B, G, 5), selected (B, L, Dp) = trajectories[b, best[b]]); a non-finite score counts as +inf."""
+    if not torch.is_tensor(trajectories) or trajectories.dim() != 4:
+        raise ValueError("trajectories must be a (B, G, L, Dp) tensor, got %s" % (
+            tuple(trajectories.shape) if torch.is_tensor(trajectories) else type(trajectories).__name__,))
+    B, G, Ln, Dp = trajectories.shape
+    if min(B, G, Ln) < 1:
+        raise ValueError("trajectories has an empty dimension: %s" % (tuple(trajectories.shape),))
+    if Dp not in (7, 8):
+        raise ValueError("trajectories rows have %d channels; pose rows have 7 or 8" % Dp)
+    if G > RANK_MAX_CANDIDATES:
+        raise ValueError("G = %d candidates per scene; the ranking serves at most %d" % (G, RANK_MAX_CANDIDATES))
+    if not torch.is_tensor(trajectory_mask) or tuple(trajectory_mask.shape) != (B, Ln):
+        raise ValueError("trajectory_mask must be (B, L) = %s, got %s" % (
+            (B, Ln), tuple(trajectory_mask.shape) if torch.is_tensor(trajectory_mask) else type(trajectory_mask).__name__))
+    if goal is not None and (not torch.is_tensor(goal) or goal.dim() != 2 or goal.shape[0] != B or goal.shape[1] < 7):
+        raise ValueError("goal must be (B, >= 7) pose rows with B = %d, got %s" % (
+            B, tuple(goal.shape) if torch.is_tensor(goal) else type(goal).__name__))
+    if bounds is not None:
+        bounds = torch.as_tensor(bounds, dtype=torch.float32, device=trajectories.device)
+        if tuple(bounds.shape) != (2, 3):
+            raise ValueError("bounds must be (2, 3), got %s" % (tuple(bounds.shape),))
+    w = check_select(select, goal is not None, bounds is not None)
+    rw = check_rot_weight(rot_weight)
+    O.L.require_gpu(trajectories, trajectory_mask, goal, bounds)
+    P = O._c(trajectories.detach().float())
+    tm = trajectory_mask.detach()
+    tm = O._c(tm).view(torch.uint8) if tm.dtype == torch.bool else O._c((tm != 0).view(torch.uint8) if tm.dtype != torch.uint8 else tm)
+    gl, ldg = (None, 0) if goal is None else _pose_rows(goal, "goal")
+    dev = P.device
+    best = torch.empty((B,), device=dev, dtype=torch.int32)
+    order = torch.empty((B, G), device=dev, dtype=torch.int32)
+    scores = torch.empty((B, G), device=dev, dtype=torch.float32)
+    terms = torch.empty((B, G, 5), device=dev, dtype=torch.float32)
+    selected = torch.empty((B, Ln, Dp), device=dev, dtype=torch.float32)
+    O.L.call("a3d_traj_rank", P.data_ptr(), tm.data_ptr(), None if gl is None else gl.data_ptr(), ldg,
+             None if bounds is None else O._c(bounds).data_ptr(), w[0], w[1], w[2], w[3], w[4], rw, best.data_ptr(), order.data_ptr(),
+             scores.data_ptr(), terms.data_ptr(), selected.data_ptr(), B, G, Ln, Dp, O.L.stream())
+    return TrajectoryRanking(best, order, scores, terms, selected)
 
 
 # ------------------------------------------------------------------------------------------------ prediction head
@@ -785,6 +880,7 @@ class DiffusionPlanner(nn.Module):
         self.register_buffer("gripper_loc_bounds", torch.tensor(gripper_loc_bounds, dtype=torch.float32), persistent=False)
         self._tables = None
         self._graph = None
+        self.last_ranking = None
 
     # ---- helpers (diffusion_model.py:187-230)
     def tables(self, device):
@@ -878,7 +974,7 @@ class DiffusionPlanner(nn.Module):
     def compute_trajectory(self, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, *,
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
                            return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None,
-                           fused_conditioning=False):
+                           fused_conditioning=False, select=None, rot_weight=1.0):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
@@ -892,12 +988,27 @@ class DiffusionPlanner(nn.Module):
         the context is expanded along the batch axis and the call runs on the single-candidate paths.
         fused_conditioning=True: the two pose conversions, the in-painting data / mask, the key mask and the noisy start trajectory
         come from ONE launch (traj_condition) instead of ~25 small ones, per trajectory of a multi-candidate call included; the
-        result is the same, bit for bit."""
+        result is the same, bit for bit.
+        select (needs num_samples): a rule of rank_trajectories (a preset name or a dict of term weights).  The G candidates are
+        ranked on the device in one launch after signal_to_pose (with use_graph: after the replay) and the call returns the
+        selected trajectory (B, L, 8), the single-trajectory shape; the goal and the workspace bounds of the ranking are this call's
+        goal_gripper and gripper_loc_bounds, rot_weight its rotation weight.  self.last_ranking keeps best / order / scores / terms /
+        selected and all candidates (B, G, L, 8).  Trace entries stay (B, G, L, D).  None (default): today's path and result."""
         head = self.prediction_head
         dev = pcd_obs.device
         B, Ln = trajectory_mask.shape
         G = None if num_samples is None else check_num_samples(num_samples)
         # host-side checks first: bad schedule arguments raise before anything is launched
+        if select is not None:
+            if G is None:
+                raise ValueError("select ranks the candidates of a num_samples=G call: give num_samples")
+            if G > RANK_MAX_CANDIDATES:
+                raise ValueError("select serves at most %d candidates per scene, num_samples is %d" % (RANK_MAX_CANDIDATES, G))
+            if curr_gripper.shape[-1] not in (7, 8):
+                raise ValueError("select ranks pose rows of 7 or 8 channels, curr_gripper has %d" % curr_gripper.shape[-1])
+            check_select(select, goal_gripper is not None, True)
+            check_rot_weight(rot_weight)
+            rank_mask, rank_goal = trajectory_mask, goal_gripper        # per scene: the fallback paths below expand their own copies
         scheduled = num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0
         if scheduled:
             K = check_sampler_args(self.n_steps, num_inference_steps, scheduler, eta)
@@ -1119,4 +1230,8 @@ class DiffusionPlanner(nn.Module):
         if G is not None:
             final = final.reshape(B_scene, G, Ln, final.shape[-1])
             trace = [x.reshape(B_scene, G, Ln, x.shape[-1]) for x in trace]
+        if select is not None:
+            rk = rank_trajectories(final, rank_mask, rank_goal, self.gripper_loc_bounds, select, rot_weight)
+            self.last_ranking = PlannerRanking(*rk, candidates=final)
+            final = rk.selected
         return (final, trace) if return_trace else final

@@ -76,6 +76,7 @@ SIGNATURES = {
     "a3d_pose_to_signal": (_i, [_p, _p, _p, _i, _i, _p]),
     "a3d_signal_to_pose": (_i, [_p, _p, _p, _i, _i, _p]),
     "a3d_traj_condition": (_i, [_p, _i, _p, _i, _p] + [_p] * 8 + [_i] * 5 + [_p]),
+    "a3d_traj_rank": (_i, [_p, _p, _p, _i, _p] + [_f] * 6 + [_p] * 5 + [_i] * 4 + [_p]),
     "a3d_traj_errors": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "a3d_keypose_errors": (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
     "a3d_sym_quat_loss": (_i, [_p, _p, _i, _f, _p, _p, _i, _p]),

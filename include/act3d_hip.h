@@ -402,6 +402,26 @@ int a3d_signal_to_pose(const float* signal, const float* bounds, float* out, int
 int a3d_traj_condition(const float* curr, int ldc, const float* goal, int ldg, const float* bounds, const unsigned char* tmask,
                        const float* init_noise, float* cg, float* gg, float* cond_data, unsigned char* cond_mask,
                        unsigned char* kmask, float* traj, int B, int G, int L, int Dp, int use_goal, void* stream);
+/* Ranks the G <= 64 sampled candidates of every scene and selects one, in one launch (one workgroup per scene; csrc/traj_rank.hip).
+ * None in the reference: Actioner.predict (online_evaluation/utils_with_rlbench.py:120-230) consumes one trajectory per scene;
+ * the distances follow TrajectoryCriterion.compute_metrics (main_trajectory.py:303-343: position L2 per step, sign-invariant
+ * quaternion distance, means over a trajectory's steps).  poses: [B][G][L][Dp], Dp = 7 or 8, rows [xyz | quat | opening]
+ * (the opening is not scored); tmask: [B][L] bytes, non-zero = padded row (any pattern), n = valid rows of the scene; goal: NULL
+ * or [B] pose rows of leading dimension ldg >= 7 floats; bounds: NULL or device [2][3].  Quaternions are divided by
+ * max(|q|, 1e-10).  d(a, b) = |p_a - p_b|_2 + rot_weight (1 - <q_a, q_b>^2).  terms[b][g] =
+ *   0 consensus  1 / max(G - 1, 1) sum_h ( 1 / max(n, 1) sum_{valid i} d(P[b,g,i], P[b,h,i]) )   (argmin = medoid;
+ *                a non-finite pair sum with h != g is left out, so one NaN candidate ranks last without spoiling the others)
+ *   1 goal       d(P[b,g,i*], goal_b), i* = highest valid row; 0 without a goal or with n = 0
+ *   2 smooth     mean over valid triples i-1, i, i+1 of |(p_{i+1} - p_i) - (p_i - p_{i-1})|^2; 0 without one
+ *   3 length     sum over valid pairs i, i+1 of |p_{i+1} - p_i|_2
+ *   4 bounds     (valid rows with a coordinate outside [lo, hi]) / max(n, 1); 0 without bounds
+ * scores[b][g] = sum_k w_k terms[b][g][k], +inf where that is not finite; order[b] = the stable ascending ranking (ties to the
+ * lower index); best[b] = order[b][0]; selected[b] = poses[b][best[b]] copied verbatim, [L][Dp].  order, scores, terms and
+ * selected may each be NULL.  Weights are finite and >= 0; a non-zero w_goal / w_bounds needs goal / bounds.  Fixed-shape
+ * reductions (no float atomics): bit-identical from run to run; bit-identical candidates score bit-identically. */
+int a3d_traj_rank(const float* poses, const unsigned char* tmask, const float* goal, int ldg, const float* bounds,
+                  float w_consensus, float w_goal, float w_smooth, float w_length, float w_bounds, float rot_weight, int* best,
+                  int* order, float* scores, float* terms, float* selected, int B, int G, int L, int Dp, void* stream);
 /* cols[b][9] of TrajectoryCriterion.compute_metrics (main_trajectory.py:303-343), see diffusion.hip; pred, gt: [B][L][D], D >= 7. */
 int a3d_traj_errors(const float* pred, const float* gt, float* cols, int B, int L, int D, void* stream);
 /* cols[b][6 + nlev] of LossAndMetrics.compute_metrics (main_keypose.py:431-482), see heads.hip; pos: [nlev + 1][B][3] with
