@@ -11,6 +11,10 @@
 //   VT format  [B][H][2][16][Npad] bf16 : plane 0 = hi, plane 1 = lo, transposed so that 8 consecutive
 //              keys of one channel are one 16-byte MFMA A-fragment.
 // Rows n >= N and slot d = 15 are written as zeros (finite padding is required by 0 * x in PV).
+// Callers of proj_rope_split_kernel: every q projection, the k | v projections of the trajectory model (E = 120) and of any block
+// whose context is read by one layer only or by another width.  The k | v rows of the keypose step's ghost-point stream (two layers
+// per pyramid level on one context, E = 60) are written by ctx_proj.hip's ctx_kv_proj_kernel since it exists -- one launch per
+// level that reads the context once; this file's kernel computes the same function and stays the A / B path (A3D_CTX_KV_BATCH=0).
 #include "a3d_common.h"
 #include "../../include/act3d_hip.h"
 #include <stdlib.h>

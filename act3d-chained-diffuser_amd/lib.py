@@ -60,6 +60,8 @@ SIGNATURES = {
     "a3d_attn_bwd_bf16": (_i, [_p] * 15 + [_i] * 7 + [_p]),
     "a3d_rope_split16": (_i, [_p, _i, _p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "a3d_proj_rope_split16": (_i, [_p, _i, _p, _i, _p, _i, _p, _f, _p, _p, _i, _p, _f, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
+    "a3d_ctx_kv_proj16_splits": (_i, [_i, _i]),
+    "a3d_ctx_kv_proj16": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "a3d_attn16_fwd": (_i, [_p] * 7 + [_i] * 7 + [_p, C.c_uint, _f, _p]),
     "a3d_attn16_fwd_rows": (_i, [_p] * 7 + [_i] * 7 + [_p, C.c_uint, _f, _i, _p]),
     "a3d_conv3x3_tile_count": (_z, [_z, _i, _i]),

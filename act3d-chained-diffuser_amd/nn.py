@@ -37,11 +37,12 @@ class RelativeCrossAttentionLayer(nn.Module):
         self.norm = nn.LayerNorm(embedding_dim)
         self.num_heads = num_heads
 
-    def forward(self, query, value, query_xyz=None, value_xyz=None, pad_mask=None, sink=None):
+    def forward(self, query, value, query_xyz=None, value_xyz=None, pad_mask=None, sink=None, kv_pair=None):
         """query (B, Lq, E), value (B, S, E) batch-first; xyz instead of materialised rotary codes.  sink: the GradSink of
-        `value` when its consumers share one gradient buffer (ops.GradSink)."""
+        `value` when its consumers share one gradient buffer (ops.GradSink).  kv_pair: this layer's k | v operand rows when the
+        caller projected the context for several layers at once (ops.ctx_kv_operands16)."""
         return O.attn_block(query, value, value, query, query_xyz, value_xyz, pad_mask, self.multihead_attn, self.norm,
-                            self.num_heads, sink=sink)
+                            self.num_heads, sink=sink, kv_pair=kv_pair)
 
 
 class FeedforwardLayer(nn.Module):
@@ -69,7 +70,16 @@ class RelativeCrossAttentionModule(nn.Module):
         """Returns the list of per-layer outputs (layers.py:345-351), batch-first."""
         output = []
         sink = getattr(value, "_a3d_sink", None)      # the context's shared gradient buffer (act3d.py attaches it), or None
-        for attn, ffw in zip(self.attn_layers, self.ffw_layers):
+        # the ghost stream: every layer projects the SAME context rows -- their k | v operands in one launch that reads them once
+        pairs = None
+        mhas = [a.multihead_attn for a in self.attn_layers]
+        if (len(mhas) > 0 and query.shape[1] != 1 and query.is_cuda and query.dtype == torch.float32 and
+                not O.query_layer_applicable(query, value, mhas[0].embed_dim, self.attn_layers[0].num_heads,
+                                             self.ffw_layers[0].linear1.out_features) and
+                all(a.num_heads == self.attn_layers[0].num_heads for a in self.attn_layers) and
+                O.ctx_kv_applicable(value, value_xyz, mhas, self.attn_layers[0].num_heads, query.shape[1])):
+            pairs = O.ctx_kv_operands16(value, value_xyz, mhas, self.attn_layers[0].num_heads)
+        for j, (attn, ffw) in enumerate(zip(self.attn_layers, self.ffw_layers)):
             mha = attn.multihead_attn
             if O.query_layer_applicable(query, value, mha.embed_dim, attn.num_heads, ffw.linear1.out_features):
                 # the one-query stream: attention block + FFN of a layer as the fused launches of csrc/query_stream.hip
@@ -78,7 +88,7 @@ class RelativeCrossAttentionModule(nn.Module):
                                              ffw.linear1.weight, ffw.linear1.bias, ffw.linear2.weight, ffw.linear2.bias,
                                              ffw.norm.weight, ffw.norm.bias, attn.num_heads, sink)
             else:
-                query = ffw(attn(query, value, query_xyz, value_xyz, sink=sink))
+                query = ffw(attn(query, value, query_xyz, value_xyz, sink=sink, kv_pair=None if pairs is None else pairs[j]))
             output.append(query)
         return output
 

@@ -217,11 +217,67 @@ def attn_operands16(q_pre_ptr, ldq, k_pre_ptr, ldk, v_pre_ptr, ldv, q_xyz, k_xyz
     return Qr, Kr, (Vr if Vp is None else Vp), Lqp, Sp, scale, freq, (Qp, Kp, Vr)
 
 
-def attn_operands_fused16(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False):
-    """attn_operands_fused for the split-fp16 kernels (a3d_proj_rope_split16)."""
+# One launch for the k | v blocks of every attention layer that reads one context (csrc/ctx_proj.hip, a3d_ctx_kv_proj16): the two
+# RelativeCrossAttentionLayers of a ghost-point pyramid level project the same context rows, and the per-layer launches read them four
+# times.  A3D_CTX_KV_BATCH=0: per-layer a3d_proj_rope_split16 launches (A/B).  Read at call time.
+CTX_KV_BATCH = os.environ.get("A3D_CTX_KV_BATCH", "1") not in ("0", "", "off")
+CTX_KV_MAX_LAYERS = 2
+
+
+def ctx_kv_applicable(value, value_xyz, mhas, H, Lq=1):
+    """Whether ctx_kv_operands16 serves these layers: the rows-only split-fp16 operand set with fused projections, the E = 60 / H = 4
+    model, fp32 device tensors, at most CTX_KV_MAX_LAYERS layers.  (Lq: the query count; a block whose backward would exceed the
+    split-fp16 backward's query limit runs on the bf16x3 family, whichever grad mode -- the operands must suit both passes.)"""
+    E = value.shape[-1]
+    if not (CTX_KV_BATCH and FUSED_PROJ and _rows_only() and _use16(Lq, True) and E == 60 and H == 4):
+        return False
+    if not (1 <= len(mhas) <= CTX_KV_MAX_LAYERS and value.is_cuda and value.dtype == F32 and value.dim() == 3):
+        return False
+    if value_xyz is not None and not (value_xyz.is_cuda and value_xyz.shape[:2] == value.shape[:2]):
+        return False
+    return all(m.in_proj_weight.dtype == F32 and m.in_proj_weight.is_cuda and m.in_proj_weight.is_contiguous() and
+               tuple(m.in_proj_weight.shape) == (3 * E, E) and m.in_proj_bias.is_contiguous() for m in mhas)
+
+
+def ctx_kv_operands16(value, value_xyz, mhas, H):
+    """(Kr, Vr) rows16 [B][H][Sp][32] of every layer in `mhas` (modules with in_proj_weight / in_proj_bias) from ONE pass over the
+    context `value` [B][S][E]: what attn_operands_fused16 writes per layer in mode "kv" (k rows rotated by value_xyz, parts 2; v rows,
+    parts 2 | 8).  Returns a list of nl (Kr, Vr) pairs."""
+    L.require_gpu(value)
+    value = _c(value)
+    B, S, E = value.shape
+    Sp = ceil_to(S, 64)
+    dev = value.device
+    freq = rope_freq(E, dev)
+    xyz = None if value_xyz is None else _c(value_xyz.to(F32))
+    pairs = [(torch.empty((B, H, Sp, 32), device=dev, dtype=torch.float16), torch.empty((B, H, Sp, 32), device=dev, dtype=torch.float16))
+             for _ in mhas]
+    f4 = 4
+    args = []
+    for j in range(CTX_KV_MAX_LAYERS):
+        if j < len(mhas):
+            w, b = mhas[j].in_proj_weight, mhas[j].in_proj_bias
+            args += [w.data_ptr() + E * E * f4, b.data_ptr() + E * f4, pairs[j][0].data_ptr(), pairs[j][1].data_ptr()]
+        else:
+            args += [None, None, None, None]
+    L.call("a3d_ctx_kv_proj16", value.data_ptr(), E, None if xyz is None else xyz.data_ptr(), *args, E, freq.data_ptr(), len(mhas),
+           B, S, Sp, E, H, 0, L.stream())
+    return pairs
+
+
+def attn_operands_fused16(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False, kv_pair=None):
+    """attn_operands_fused for the split-fp16 kernels (a3d_proj_rope_split16).  kv_pair: the (Kr, Vr) rows of this layer already
+    written by ctx_kv_operands16 (mode "kv", rows-only set): only q is projected here."""
     Lqp, Sp = ceil_to(Lq, 64), ceil_to(S, 64)
     scale = float(E // H) ** -0.5 * LOG2E
     freq = rope_freq(E, device)
+    if kv_pair is not None:
+        Kr, Vr = kv_pair
+        Qr = torch.empty((B, H, Lqp, 32), device=device, dtype=torch.float16)
+        L.call("a3d_proj_rope_split16", q_in.data_ptr(), E, wp, E, bp, E,
+               None if q_xyz is None else q_xyz.data_ptr(), scale, Qr.data_ptr(), None, PLANE_PARTS, None, 1.0, None, None, 1,
+               freq.data_ptr(), B, Lq, Lqp, E, H, L.stream())
+        return Qr, Kr, Vr, Lqp, Sp, scale, freq, (None, None, Vr)
     Qr, Kr, Vp, Qp, Kp, Vr = _alloc16(B, H, Lqp, Sp, device, need_bwd)
     st = L.stream()
     f4 = 4
@@ -605,12 +661,13 @@ class AttnBlockFn(torch.autograd.Function):
     """
     @staticmethod
     def forward(ctx, q_in, k_in, v_in, resid, q_xyz, k_xyz, kmask, in_w, in_b, out_w, out_b, ln_g, ln_b, H, mode,
-                drop=None, site=0, grad_mode=True, sink=None, q_is_resid=False):
+                drop=None, site=0, grad_mode=True, sink=None, q_is_resid=False, kv_pair=None):
         """q_is_resid: the caller passed the SAME tensor object as query and residual (decided at the call site, `q_in is resid`:
         two distinct autograd tensors that merely share storage -- a detached leaf, a view alias -- keep separate gradients).
         drop / site: DropCtx of the pass and this block's site id (attention weights: site, residual branch: site + 1;
         multihead_custom_attention.py:413, layers.py:146,181).  grad_mode: torch.is_grad_enabled() of the CALLER (grad mode is
-        always off inside Function.forward, so it has to be handed in; attn_block does)."""
+        always off inside Function.forward, so it has to be handed in; attn_block does).  kv_pair: this layer's (Kr, Vr) rows from
+        ops.ctx_kv_operands16 (the caller checked ops.ctx_kv_applicable), or None."""
         L.require_gpu(q_in, k_in, v_in, resid)
         if drop is not None and drop.p <= 0:
             drop = None
@@ -627,7 +684,13 @@ class AttnBlockFn(torch.autograd.Function):
         # whether a backward can follow: the in-projection parameters count (they get .grad through wgrad even when no
         # input needs a gradient); under torch.no_grad() none follows whatever the parameters say
         need_bwd = bool(grad_mode) and (any(ctx.needs_input_grad) or in_w.requires_grad)
-        if FUSED_PROJ and E % 4 == 0 and E <= 128:
+        if kv_pair is not None:
+            # ---- k | v rows written once for all layers of this context; only q is projected here
+            if mode != "kv":
+                raise RuntimeError("AttnBlockFn: precomputed context operands need the packed k,v projection (key is value)")
+            Qs, Ks, Vt, Lqp, Sp, scale, freq, extra = attn_operands_fused16(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S,
+                                                                            E, H, dev, need_bwd, kv_pair=kv_pair)
+        elif FUSED_PROJ and E % 4 == 0 and E <= 128:
             # ---- projections fused with RoPE + operand formatting: the projected rows never reach HBM
             fused = attn_operands_fused16 if _use16(Lq, need_bwd) else attn_operands_fused
             Qs, Ks, Vt, Lqp, Sp, scale, freq, extra = fused(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, dev,
@@ -774,7 +837,7 @@ class AttnBlockFn(torch.autograd.Function):
                 if need_v:
                     d_v_in = dgrad2d(dv_pre, in_w[2 * E:]).view(B, S, E)
         d_resid = dS.view(B, Lq, E) if ctx.needs_input_grad[3] else None
-        return (d_q_in, d_k_in, d_v_in, d_resid) + (None,) * 16
+        return (d_q_in, d_k_in, d_v_in, d_resid) + (None,) * 17
 
 
 SINGLE_QUERY = os.environ.get("A3D_SINGLE_QUERY", "1") == "1"
@@ -960,7 +1023,7 @@ def query_layer_applicable(query, value, E, H, hidden):
             H * 15 == E and hidden == E and value.dtype == F32 and query.dtype == F32)
 
 
-def attn_block(q_in, k_in, v_in, resid, q_xyz, k_xyz, kmask, mha, norm, H, drop=None, site=0, sink=None):
+def attn_block(q_in, k_in, v_in, resid, q_xyz, k_xyz, kmask, mha, norm, H, drop=None, site=0, sink=None, kv_pair=None):
     """mha: module with in_proj_weight/in_proj_bias/out_proj; norm: LayerNorm-like with weight/bias.
 
     The projection path is chosen structurally (which inputs are the same tensor), replacing the reference's
@@ -978,7 +1041,7 @@ def attn_block(q_in, k_in, v_in, resid, q_xyz, k_xyz, kmask, mha, norm, H, drop=
         mode = "none"
     return AttnBlockFn.apply(q_in, k_in, v_in, resid, q_xyz, k_xyz, kmask, mha.in_proj_weight, mha.in_proj_bias,
                              mha.out_proj.weight, mha.out_proj.bias, norm.weight, norm.bias, H, mode, drop, site,
-                             torch.is_grad_enabled(), sink, q_in is resid)
+                             torch.is_grad_enabled(), sink, q_in is resid, kv_pair)
 
 
 class MLPFn(torch.autograd.Function):

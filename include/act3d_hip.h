@@ -150,6 +150,16 @@ int a3d_rope_split16(const float* Y, int ldy, const float* xyz, const float* fre
 int a3d_proj_rope_split16(const float* X, int ldx, const float* W, int ldw, const float* bias, int K, const float* xyz0,
                           float scale0, void* rows0, void* planes0, int parts0, const float* xyz1, float scale1, void* rows1,
                           void* planes1, int parts1, const float* freq, int B, int N, int Npad, int E, int H, void* stream);
+/* The k | v blocks of nl = 1 or 2 attention layers that read the SAME context rows X [B][N][E] (row stride ldx), in one launch
+ * (csrc/ctx_proj.hip): X is read once, every layer's K rows (rotated by xyz, parts 2) and V rows (parts 2 | 8) are written in the rows16
+ * format with the pad convention above.  Wl / biasl: rows [E, 3E) of layer l's in_proj_weight (row stride ldw) / in_proj_bias, i.e.
+ * W_k | W_v (4-byte aligned; bias may be NULL); layer 1's arguments are ignored when nl == 1.  xyz [B][N][3] or NULL (no rotation).
+ * E = 60, H = 4 only; anything else is refused with the error code (the caller then uses a3d_proj_rope_split16 per layer, which
+ * computes the same function).  nsplit: workgroups per sample, 0 = a3d_ctx_kv_proj16_splits(B, Npad). */
+int a3d_ctx_kv_proj16_splits(int B, int Npad);
+int a3d_ctx_kv_proj16(const float* X, int ldx, const float* xyz, const float* W0, const float* bias0, void* Krows0, void* Vrows0,
+                      const float* W1, const float* bias1, void* Krows1, void* Vrows1, int ldw, const float* freq, int nl, int B,
+                      int N, int Npad, int E, int H, int nsplit, void* stream);
 /* O [B][Lq][E] fp32, LSE2 [B][H][Lqp] fp32 (log2 units).  Qr, Kr rows16; Vp planes16 with BOTH parts.  ws as a3d_attn_fwd. */
 int a3d_attn16_fwd(const void* Qr, const void* Kr, const void* Vp, const unsigned char* kmask, float* O, float* LSE2,
                    float* ws, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit,

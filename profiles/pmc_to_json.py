@@ -19,6 +19,7 @@ GROUPS = {
     "attn_fwd_bf16x3": ["attn_fwd_kernel", "attn_combine_kernel"],
     "attn_bwd_bf16x3": ["attn_bwd_prep_bf16_kernel", "attn_bwd_dq_bf16_kernel", "attn_bwd_dkv_bf16_kernel"],
     "kv_proj_rope": ["proj_rope_split_kernel"],
+    "ctx_kv_proj": ["ctx_kv_proj_kernel"],
     "sq_fwd": ["sq_fwd_kernel", "sqw_fwd_kernel", "sq_combine_kernel"],
     "sq_bwd": ["sq_bwd_kernel", "sqw_bwd_kernel"],
     "dn_cross": ["dn_cross_kernel"],
