@@ -589,7 +589,7 @@ class DiffusionHead(nn.Module):
 
     # ---- inference, fused: 18 launches per network evaluation (csrc/denoise.hip)
     @torch.no_grad()
-    def build_fused(self, ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=True, n_cand=1):
+    def build_fused(self, ctx, ctx_xyz, instr, kmask, time_sin, Ln, n_cand=1):
         """Step-invariant state of the fused sampling path for one trajectory batch: the context K (fp16 hi | lo rows) / V (fp16
         hi / lo planes) of every cross-attention layer, the instruction tokens through traj_lang_attention's k | v projection, and
         the AdaLN modulation of every layer at every row of time_sin (Linear(SiLU(sinusoidal(t))), layers.py:273-290): all T timesteps
@@ -632,45 +632,73 @@ class DiffusionHead(nn.Module):
         nws = O.L.load().a3d_dn_cross_ws_floats(B, H, st["nsplit"])
         st["ws"] = torch.empty((nws,), device=dev, dtype=torch.float32)
         st["ws_side"] = torch.empty((nws,), device=dev, dtype=torch.float32)      # rotation branch, concurrent
-        # with_persist=False: the caller is about to replay a captured graph that owns its persistent-sampler state (tables, exchange
-        # buffers, synchronisation words) -- only the refreshed K / V / modulation tensors of this call are needed
-        st["persist"] = self._build_persist(st, B * n_cand, Ln, H, E, Sp, time_sin.shape[0], dev) if (DN_PERSIST and with_persist) else None
+        st["persist"] = None                                # the persistent sampler's own state: _build_persist, for the calls planned on it
         return st
 
-    def persist_fits(self, B, Ln, dev):
-        """Whether the persistent sampler can serve B trajectories of Ln steps: two sample-role workgroups per (trajectory, 16-step
-        row tile) -- primary + rotation-stack helper -- and >= 16 streamers, all co-resident."""
-        NT = -(-Ln // 16)
-        return not (2 * B * NT + 16 > torch.cuda.get_device_properties(dev).multi_processor_count or self.num_attn_heads > 8 or NT > 4)
+    # ---- the parameter blocks of the fused kernels (lib.Dn*Params), each built in ONE place
+    def _dn_head_params(self, st):
+        enc = self.traj_encoder
+        hp = O.L.DnHeadParams(enc_w0=enc[0].weight.data_ptr(), enc_b0=enc[0].bias.data_ptr(), enc_w1=enc[3].weight.data_ptr(),
+                              enc_b1=enc[3].bias.data_ptr(), sem=st["sem"].data_ptr(),
+                              lang_kv=None if st["lang_kv"] is None else st["lang_kv"].data_ptr(), S_lang=st.get("S_lang", 0))
+        if st["lang_kv"] is not None:
+            ll = self.traj_lang_attention[0].layers[0]
+            hp.q_w, hp.q_b = ll.cross_12.in_proj_weight.data_ptr(), ll.cross_12.in_proj_bias.data_ptr()
+            hp.out_w, hp.out_b = ll.cross_12.out_proj.weight.data_ptr(), ll.cross_12.out_proj.bias.data_ptr()
+            hp.ln_g, hp.ln_b = ll.norm_12.weight.data_ptr(), ll.norm_12.bias.data_ptr()
+        return hp
 
-    def _build_persist(self, st, B, Ln, H, E, Sp, T, dev):
+    def _dn_tail_params(self, noise, cond_data, cond_mask_u8, tables):
+        """noise: what the launch reads -- the whole table (persistent sampler), one step's row (per-phase tail) or None."""
+        pr, rr = self.pos_regressor[0], self.rot_regressor[0]
+        return O.L.DnTailParams(pos_w0=pr[0].weight.data_ptr(), pos_b0=pr[0].bias.data_ptr(), pos_w1=pr[3].weight.data_ptr(),
+                                pos_b1=pr[3].bias.data_ptr(), rot_w0=rr[0].weight.data_ptr(), rot_b0=rr[0].bias.data_ptr(),
+                                rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(),
+                                noise=None if noise is None else noise.data_ptr(), cond_data=cond_data.data_ptr(),
+                                cond_mask=cond_mask_u8.data_ptr(), coef_pos=tables.coef_pos.data_ptr(),
+                                coef_rot=tables.coef_rot.data_ptr())
+
+    @staticmethod
+    def _dn_mod(rec, k, row):
+        """AdaLN table k ([rows][2E] fp32) of a layer: its base for row=None (the persistent sampler indexes it with the step), else
+        the pointer to `row`."""
+        m = rec["mods"][k]
+        return m.data_ptr() + (0 if row is None else row * m.stride(0) * m.element_size())
+
+    def _dn_cross_params(self, st, rec, row=None):
+        mha = rec["lay"].cross_12
+        return O.L.DnCrossParams(sem=st["sem"].data_ptr(), mod=self._dn_mod(rec, 0, row), q_w=mha.in_proj_weight.data_ptr(),
+                                 q_b=mha.in_proj_bias.data_ptr(), freq=st["freq"].data_ptr(), Kf=rec["Kf"].data_ptr(),
+                                 Vt=rec["Vt"].data_ptr())
+
+    def _dn_rest_params(self, st, rec, row=None):
+        lay, ff = rec["lay"], rec["lay"].ffn_12
+        return O.L.DnRestParams(
+            c_out_w=lay.cross_12.out_proj.weight.data_ptr(), c_out_b=lay.cross_12.out_proj.bias.data_ptr(),
+            c_ln_g=lay.norm_12.weight.data_ptr(), c_ln_b=lay.norm_12.bias.data_ptr(), sem=st["sem"].data_ptr(),
+            s_mod=self._dn_mod(rec, 1, row), s_in_w=lay.sa1.in_proj_weight.data_ptr(), s_in_b=lay.sa1.in_proj_bias.data_ptr(),
+            s_out_w=lay.sa1.out_proj.weight.data_ptr(), s_out_b=lay.sa1.out_proj.bias.data_ptr(),
+            s_ln_g=lay.norm_1.weight.data_ptr(), s_ln_b=lay.norm_1.bias.data_ptr(), freq=st["freq"].data_ptr(),
+            kmask=None if st["kmask"] is None else st["kmask"].data_ptr(), f_mod=self._dn_mod(rec, 2, row),
+            f_w1=ff[0].weight.data_ptr(), f_b1=ff[0].bias.data_ptr(), f_w2=ff[3].weight.data_ptr(), f_b2=ff[3].bias.data_ptr(),
+            f_ln_g=lay.norm_122.weight.data_ptr(), f_ln_b=lay.norm_122.bias.data_ptr(), F=ff[0].weight.shape[0])
+
+    def _build_persist(self, st, B, Ln, T, group=False):
         """State of the persistent sampler (a3d_dn_persist: the whole denoise loop as one launch, csrc/denoise.hip): the device
         table of per-layer parameter blocks (AdaLN tables by their base: the kernel indexes them with the step), the query /
-        partial exchange buffers and the synchronisation words.  None when the batch leaves too few CUs for the streaming role.
+        partial exchange buffers and the synchronisation words.  Whether the launch fits the device is sampler_plan's question
+        (persist_fits), answered before this state is built.
         B: TRAJECTORIES (scenes x st["n_cand"] candidates: the workspaces are per trajectory, the K / V tables of st per scene).
-        T: rows of the AdaLN tables -- the training timesteps, or the K steps of a sampler schedule (a3d_dn_persist_sched)."""
-        import ctypes
+        T: rows of the AdaLN tables -- the training timesteps, or the K steps of a sampler schedule (a3d_dn_persist_sched).
+        group: the launches go through a3d_dn_persist_group (compute_trajectory(num_samples=...))."""
         Lb = O.L
         lib = Lb.load()
+        H, E, Sp, dev = self.num_attn_heads, st["sem"].shape[-1], st["Sp"], st["sem"].device
         NT = -(-Ln // 16)                                   # 16-step row tiles per trajectory: one sample-role workgroup each
-        if not self.persist_fits(B, Ln, dev):
-            return None
         recs = st["layers"]
         table = (Lb.DnLayerParams * len(recs))()
         for i, rec in enumerate(recs):
-            lay, mods, ff = rec["lay"], rec["mods"], rec["lay"].ffn_12
-            table[i].cross = Lb.DnCrossParams(
-                sem=st["sem"].data_ptr(), mod=mods[0].data_ptr(), q_w=lay.cross_12.in_proj_weight.data_ptr(),
-                q_b=lay.cross_12.in_proj_bias.data_ptr(), freq=st["freq"].data_ptr(), Kf=rec["Kf"].data_ptr(), Vt=rec["Vt"].data_ptr())
-            table[i].rest = Lb.DnRestParams(
-                c_out_w=lay.cross_12.out_proj.weight.data_ptr(), c_out_b=lay.cross_12.out_proj.bias.data_ptr(),
-                c_ln_g=lay.norm_12.weight.data_ptr(), c_ln_b=lay.norm_12.bias.data_ptr(), sem=st["sem"].data_ptr(),
-                s_mod=mods[1].data_ptr(), s_in_w=lay.sa1.in_proj_weight.data_ptr(), s_in_b=lay.sa1.in_proj_bias.data_ptr(),
-                s_out_w=lay.sa1.out_proj.weight.data_ptr(), s_out_b=lay.sa1.out_proj.bias.data_ptr(),
-                s_ln_g=lay.norm_1.weight.data_ptr(), s_ln_b=lay.norm_1.bias.data_ptr(), freq=st["freq"].data_ptr(),
-                kmask=None if st["kmask"] is None else st["kmask"].data_ptr(), f_mod=mods[2].data_ptr(), f_w1=ff[0].weight.data_ptr(),
-                f_b1=ff[0].bias.data_ptr(), f_w2=ff[3].weight.data_ptr(), f_b2=ff[3].bias.data_ptr(),
-                f_ln_g=lay.norm_122.weight.data_ptr(), f_ln_b=lay.norm_122.bias.data_ptr(), F=ff[0].weight.shape[0])
+            table[i].cross, table[i].rest = self._dn_cross_params(st, rec), self._dn_rest_params(st, rec)
         raw = bytes(memoryview(table))
         nsplit = max(1, min(DN_PERSIST_SPLIT, Sp // 64, 16 // lib.a3d_dn_persist_splits(H, 1)))      # at most 16 partials per (sample, head)
         nse = lib.a3d_dn_persist_splits(H, nsplit)
@@ -685,110 +713,71 @@ class DiffusionHead(nn.Module):
             "sync": torch.zeros((lib.a3d_dn_persist_sync_ints(B, Ln, n_layers, T),), device=dev, dtype=torch.int32),
             "stacks": (len(self.traj_attention[0].layers), len(self.pos_attention[0].layers), len(self.rot_attention[0].layers)),
             "rows": T,                                          # rows of the AdaLN tables = the most steps one launch may run
-            "n_cand": st.get("n_cand", 1),                      # candidates per scene: > 1 or a num_samples call -> a3d_dn_persist_group
-            "group": False,
+            "n_cand": st.get("n_cand", 1),                      # candidates per scene of a num_samples call
+            "group": group,
         }
 
     @torch.no_grad()
-    def fused_persist(self, st, traj, t_first, nsteps, step_noise, cond_data, cond_mask_u8, tb, sched=None):
-        """nsteps consecutive denoise steps t_first, t_first - 1, ... (network evaluation + DDPM reverse step each) as ONE launch of
-        the persistent sampler; returns the trajectory after the last of them (a new tensor).  step_noise: the (T, B, L, D) table.
-        sched (a SamplerSchedule; st built on its timesteps): the steps at POSITIONS t_first, t_first + 1, ... of the schedule
-        (a3d_dn_persist_sched); step_noise is then (K, B, L, D) by position, or None for a noise-free schedule.
+    def fused_persist(self, st, traj, first, nsteps, step_noise, cond_data, cond_mask_u8, tables):
+        """nsteps consecutive denoise steps (network evaluation + DDPM reverse step each) as ONE launch of the persistent sampler;
+        returns the trajectory after the last of them (a new tensor).  tables is what st was built on:
+        a DDPMTables -- the timesteps first, first - 1, ... of the full chain (a3d_dn_persist), step_noise the (T, B, L, D) table;
+        a SamplerSchedule -- the steps at POSITIONS first, first + 1, ... of the schedule (a3d_dn_persist_sched), step_noise
+        (K, B, L, D) by position, or None for a noise-free schedule.
         A state marked for candidate groups (ps["group"]: compute_trajectory(num_samples=G), always on a schedule) goes through
         a3d_dn_persist_group: traj holds scenes x n_cand trajectories, scene-major, against the per-scene cache of st."""
         Lb = O.L
         ps = st["persist"]
         B, Ln, D = traj.shape
-        H = self.num_attn_heads
-        E = self.curr_gripper_embed.weight.shape[1]
-        hp = Lb.DnHeadParams(enc_w0=self.traj_encoder[0].weight.data_ptr(), enc_b0=self.traj_encoder[0].bias.data_ptr(),
-                             enc_w1=self.traj_encoder[3].weight.data_ptr(), enc_b1=self.traj_encoder[3].bias.data_ptr(),
-                             sem=st["sem"].data_ptr(), lang_kv=None if st["lang_kv"] is None else st["lang_kv"].data_ptr(),
-                             S_lang=st.get("S_lang", 0))
-        if st["lang_kv"] is not None:
-            ll = self.traj_lang_attention[0].layers[0]
-            hp.q_w, hp.q_b = ll.cross_12.in_proj_weight.data_ptr(), ll.cross_12.in_proj_bias.data_ptr()
-            hp.out_w, hp.out_b = ll.cross_12.out_proj.weight.data_ptr(), ll.cross_12.out_proj.bias.data_ptr()
-            hp.ln_g, hp.ln_b = ll.norm_12.weight.data_ptr(), ll.norm_12.bias.data_ptr()
-        pr, rr = self.pos_regressor[0], self.rot_regressor[0]
-        tp = Lb.DnTailParams(pos_w0=pr[0].weight.data_ptr(), pos_b0=pr[0].bias.data_ptr(), pos_w1=pr[3].weight.data_ptr(),
-                             pos_b1=pr[3].bias.data_ptr(), rot_w0=rr[0].weight.data_ptr(), rot_b0=rr[0].bias.data_ptr(),
-                             rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(),
-                             noise=None if step_noise is None else step_noise.data_ptr(),
-                             cond_data=cond_data.data_ptr(), cond_mask=cond_mask_u8.data_ptr(), coef_pos=tb.coef_pos.data_ptr(),
-                             coef_rot=tb.coef_rot.data_ptr())
+        hp, tp = self._dn_head_params(st), self._dn_tail_params(step_noise, cond_data, cond_mask_u8, tables)
         out = traj.clone()
         self._last_persist = ps                      # tests read the abort word (sync[2]) after synchronising
         nt, npos, nrot = ps["stacks"]
-        common = (ps["table"].data_ptr(), nt, npos, nrot, C_byref(hp), C_byref(tp), out.data_ptr(), ps["qbuf"].data_ptr(),
+        common = (ps["table"].data_ptr(), nt, npos, nrot, O.C_byref(hp), O.C_byref(tp), out.data_ptr(), ps["qbuf"].data_ptr(),
                   ps["part"].data_ptr(), None if ps["kvx"] is None else ps["kvx"].data_ptr(), ps["xbuf"].data_ptr(), ps["sync"].data_ptr(),
-                  B, Ln, D, E, H, st["S"], st["Sp"], ps["nsplit"], int(t_first), int(nsteps))
-        if sched is None:
+                  B, Ln, D, st["sem"].shape[-1], self.num_attn_heads, st["S"], st["Sp"], ps["nsplit"], int(first), int(nsteps))
+        if not isinstance(tables, SamplerSchedule):
             entry = "a3d_dn_persist"
             assert not ps["group"]
             Lb.call(entry, *common, Lb.stream())
         else:
-            assert tb is sched and ps["rows"] == sched.K and (step_noise is None) == sched.noise_free
+            K = tables.K
+            assert ps["rows"] == K and (step_noise is None) == tables.noise_free
             if ps["group"]:
                 entry = "a3d_dn_persist_group"
                 assert B % ps["n_cand"] == 0 and st["layers"][0]["Kf"].shape[0] * ps["n_cand"] == B
-                Lb.call(entry, *common, sched.K, int(t_first + nsteps == sched.K), ps["n_cand"], Lb.stream())
+                Lb.call(entry, *common, K, int(first + nsteps == K), ps["n_cand"], Lb.stream())
             else:
                 entry = "a3d_dn_persist_sched"
-                Lb.call(entry, *common, sched.K, int(t_first + nsteps == sched.K), Lb.stream())
+                Lb.call(entry, *common, K, int(first + nsteps == K), Lb.stream())
         if DN_PERSIST_CHECK:
             if int(ps["sync"][2].item()) != 0:
                 raise RuntimeError(entry + " gave up waiting (sync[2] != 0): the trajectory is invalid")
         return out
 
     @torch.no_grad()
-    def fused_step(self, st, traj, t, noise, cond_data, cond_mask_u8, tb, terminal=None):
-        """One denoise step: network evaluation at timestep t + DDPM reverse step -> the next trajectory (B, L, D).
-        terminal (bool) given: t is the step's POSITION in a SamplerSchedule (st and tb built on it) and terminal says whether the
-        step returns the in-painted network output (a3d_dn_tail_sched)."""
+    def fused_step(self, st, traj, row, noise, cond_data, cond_mask_u8, tables):
+        """One denoise step: network evaluation + DDPM reverse step -> the next trajectory (B, L, D).  tables is what st was built
+        on: a DDPMTables -- row is the timestep (a3d_dn_tail); a SamplerSchedule -- row is the step's POSITION, and the step at
+        position K - 1 returns the in-painted network output (a3d_dn_tail_sched).  noise: this step's (B, L, D) draw or None."""
         Lb = O.L
         out = torch.empty_like(traj)
         B, Ln, D = traj.shape
         H = self.num_attn_heads
-        E = self.curr_gripper_embed.weight.shape[1]
+        E = st["sem"].shape[-1]
         dev = traj.device
-        f4 = 4
-        nz = lambda x: None if x is None else x.data_ptr()
         new = lambda: torch.empty((B, Ln, E), device=dev, dtype=torch.float32)
-        hp = Lb.DnHeadParams(enc_w0=self.traj_encoder[0].weight.data_ptr(), enc_b0=self.traj_encoder[0].bias.data_ptr(),
-                             enc_w1=self.traj_encoder[3].weight.data_ptr(), enc_b1=self.traj_encoder[3].bias.data_ptr(),
-                             sem=st["sem"].data_ptr(), lang_kv=None if st["lang_kv"] is None else st["lang_kv"].data_ptr(),
-                             S_lang=st.get("S_lang", 0))
-        if st["lang_kv"] is not None:
-            ll = self.traj_lang_attention[0].layers[0]
-            hp.q_w, hp.q_b = ll.cross_12.in_proj_weight.data_ptr(), ll.cross_12.in_proj_bias.data_ptr()
-            hp.out_w, hp.out_b = ll.cross_12.out_proj.weight.data_ptr(), ll.cross_12.out_proj.bias.data_ptr()
-            hp.ln_g, hp.ln_b = ll.norm_12.weight.data_ptr(), ll.norm_12.bias.data_ptr()
+        hp = self._dn_head_params(st)
         x = new()
-        Lb.call("a3d_dn_head", traj.data_ptr(), D, C_byref(hp), x.data_ptr(), B, Ln, E, H, Lb.stream())
+        Lb.call("a3d_dn_head", traj.data_ptr(), D, O.C_byref(hp), x.data_ptr(), B, Ln, E, H, Lb.stream())
 
         def run_layer(xin, rec, ws):
-            lay = rec["lay"]
             stream = Lb.stream()
-            mo = [m.data_ptr() + t * 2 * E * f4 for m in rec["mods"]]
-            cp = Lb.DnCrossParams(sem=st["sem"].data_ptr(), mod=mo[0], q_w=lay.cross_12.in_proj_weight.data_ptr(),
-                                  q_b=lay.cross_12.in_proj_bias.data_ptr(), freq=st["freq"].data_ptr(), Kf=rec["Kf"].data_ptr(),
-                                  Vt=rec["Vt"].data_ptr())
-            Lb.call("a3d_dn_cross", xin.data_ptr(), traj.data_ptr(), D, C_byref(cp), ws.data_ptr(), B, Ln, E, H, st["S"],
+            cp, rp = self._dn_cross_params(st, rec, row), self._dn_rest_params(st, rec, row)
+            Lb.call("a3d_dn_cross", xin.data_ptr(), traj.data_ptr(), D, O.C_byref(cp), ws.data_ptr(), B, Ln, E, H, st["S"],
                     st["Sp"], st["nsplit"], stream)
-            ff = lay.ffn_12
-            rp = Lb.DnRestParams(
-                c_out_w=lay.cross_12.out_proj.weight.data_ptr(), c_out_b=lay.cross_12.out_proj.bias.data_ptr(),
-                c_ln_g=lay.norm_12.weight.data_ptr(), c_ln_b=lay.norm_12.bias.data_ptr(), sem=st["sem"].data_ptr(),
-                s_mod=mo[1], s_in_w=lay.sa1.in_proj_weight.data_ptr(), s_in_b=lay.sa1.in_proj_bias.data_ptr(),
-                s_out_w=lay.sa1.out_proj.weight.data_ptr(), s_out_b=lay.sa1.out_proj.bias.data_ptr(),
-                s_ln_g=lay.norm_1.weight.data_ptr(), s_ln_b=lay.norm_1.bias.data_ptr(), freq=st["freq"].data_ptr(),
-                kmask=None if st["kmask"] is None else st["kmask"].data_ptr(), f_mod=mo[2], f_w1=ff[0].weight.data_ptr(), f_b1=ff[0].bias.data_ptr(),
-                f_w2=ff[3].weight.data_ptr(), f_b2=ff[3].bias.data_ptr(), f_ln_g=lay.norm_122.weight.data_ptr(),
-                f_ln_b=lay.norm_122.bias.data_ptr(), F=ff[0].weight.shape[0])
             xout = new()
-            Lb.call("a3d_dn_rest", xin.data_ptr(), traj.data_ptr(), D, ws.data_ptr(), C_byref(rp), xout.data_ptr(), B, Ln,
+            Lb.call("a3d_dn_rest", xin.data_ptr(), traj.data_ptr(), D, ws.data_ptr(), O.C_byref(rp), xout.data_ptr(), B, Ln,
                     E, H, st["nsplit"], stream)
             return xout
 
@@ -812,19 +801,12 @@ class DiffusionHead(nn.Module):
             pf = run_layer(pf, rec, st["ws"])
         cur.wait_stream(side)
         rf.record_stream(cur)
-        stream = Lb.stream()
-        pr, rr = self.pos_regressor[0], self.rot_regressor[0]
-        tp = Lb.DnTailParams(pos_w0=pr[0].weight.data_ptr(), pos_b0=pr[0].bias.data_ptr(), pos_w1=pr[3].weight.data_ptr(),
-                             pos_b1=pr[3].bias.data_ptr(), rot_w0=rr[0].weight.data_ptr(), rot_b0=rr[0].bias.data_ptr(),
-                             rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(), noise=nz(noise),
-                             cond_data=cond_data.data_ptr(), cond_mask=cond_mask_u8.data_ptr(), coef_pos=tb.coef_pos.data_ptr(),
-                             coef_rot=tb.coef_rot.data_ptr())
-        if terminal is None:
-            Lb.call("a3d_dn_tail", pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, C_byref(tp), out.data_ptr(), B, Ln, E,
-                    int(t), stream)
+        tp = self._dn_tail_params(noise, cond_data, cond_mask_u8, tables)
+        tail = (pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, O.C_byref(tp), out.data_ptr(), B, Ln, E, int(row))
+        if not isinstance(tables, SamplerSchedule):
+            Lb.call("a3d_dn_tail", *tail, Lb.stream())
         else:
-            Lb.call("a3d_dn_tail_sched", pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, C_byref(tp), out.data_ptr(), B, Ln, E,
-                    int(t), int(bool(terminal)), stream)
+            Lb.call("a3d_dn_tail_sched", *tail, int(row == tables.K - 1), Lb.stream())
         return out
 
 
@@ -846,6 +828,11 @@ DN_PERSIST_CHECK = os.environ.get("A3D_DN_PERSIST_CHECK", "0") == "1"
 _DN_SIDE = {}
 
 
+def _as_list(x):
+    """Per-scale tensors as a list: a single-scale head passes the bare tensor."""
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
 def _dn_side_stream(dev):
     key = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
     if key not in _DN_SIDE:
@@ -853,9 +840,57 @@ def _dn_side_stream(dev):
     return _DN_SIDE[key]
 
 
-def C_byref(struct):
-    import ctypes
-    return ctypes.byref(struct)
+def persist_fits(n_traj, Ln, H, cus):
+    """Whether the persistent sampler can serve n_traj trajectories of Ln steps on a device of `cus` compute units: two sample-role
+    workgroups per (trajectory, 16-step row tile) -- primary + rotation-stack helper -- and >= 16 streamers, all co-resident; at most
+    four row tiles and eight heads."""
+    NT = -(-Ln // 16)
+    return 2 * n_traj * NT + 16 <= cus and H <= 8 and NT <= 4
+
+
+# path: "multi-round" | "persistent" | "per-phase" | "op-by-op"; group: candidate groups on the per-scene cache (a3d_dn_persist_group);
+# scheduled / K: tables by step position, K rows (else by timestep, K None); flip_noise: the by-timestep noise of a full chain is read
+# in step order; steps: the timesteps to run; label: what last_sampler_path reports
+SamplerPlan = collections.namedtuple("SamplerPlan", ("path", "group", "scheduled", "K", "flip_noise", "steps", "label"))
+
+
+def sampler_plan(B, G, Ln, D, E, H, T, cus, multi=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0,
+                 n_steps=None):
+    """Which launches serve a compute_trajectory call, from host values alone: B scenes x G candidates (G None: one trajectory per
+    scene, no candidate axis) of Ln steps and D signal channels, embedding E, H heads, T training timesteps, a device of `cus`
+    compute units; multi: a multi-round / multi-scale head; the other arguments are compute_trajectory's.
+
+      multi-round   a multi-round head: nothing but the image encoding is step-invariant, every step evaluates the full head
+      persistent    the fused kernels serve the shape (`fused` below: E, D and the L x D tile they stage), A3D_DN_PERSIST and persist_fits:
+                    the whole loop is one launch -- a3d_dn_persist (full chain), a3d_dn_persist_sched (schedule) or, with G,
+                    a3d_dn_persist_group on the per-scene cache (the full chain then runs as the K = T "ddpm" schedule: the same
+                    coefficients and AdaLN rows, bit for bit, with the noise of timestep t at row T - 1 - t)
+      per-phase     the fused kernels serve the shape and L <= 16 (one row tile): 2 + 2 * layers launches per step
+      op-by-op      everything else: the K/V cache and one launch per operation
+
+    With G and any path but the persistent one the context is expanded along the batch axis (group False).  The module switches
+    are read here, at call time."""
+    scheduled = num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0
+    K = check_sampler_args(T, num_inference_steps, scheduler, eta) if scheduled else None
+    fused = (FUSED_DENOISE if fused is None else fused) and E <= 128 and D <= 16 and min(Ln, 16) * D <= 160
+    if multi:
+        path = "multi-round"
+    elif fused and DN_PERSIST and persist_fits(B * (G or 1), Ln, H, cus):
+        path = "persistent"
+    elif fused and Ln <= 16:
+        path = "per-phase"
+    else:
+        path = "op-by-op"
+    group = G is not None and path == "persistent"
+    flip_noise = group and not scheduled
+    if flip_noise:
+        scheduled, K = True, T
+    steps = sampler_timesteps(T, K)[0] if scheduled else list(range(T - 1, -1, -1))
+    if n_steps is not None:
+        steps = steps[:n_steps]
+    label = {"multi-round": "multi-round", "per-phase": "per-phase fused launches", "op-by-op": "op-by-op",
+             "persistent": "persistent (a3d_dn_persist%s)" % ("_group" if group else "_sched" if scheduled else "")}[path]
+    return SamplerPlan(path, group, scheduled, K, flip_noise, tuple(steps), label)
 
 
 class DiffusionPlanner(nn.Module):
@@ -956,9 +991,7 @@ class DiffusionPlanner(nn.Module):
             noisy = O.ddpm_add_noise(gt, noise.to(dev).float()[..., :9].contiguous(), timesteps.to(dev), tb.acp_pos, tb.acp_rot)
         if head.attn_rounds * head.feat_scales > 1:
             # every iteration's prediction is supervised (diffusion_model.py:313-323)
-            toks = tokens if isinstance(tokens, (list, tuple)) else [tokens]
-            xyzs = ctx_xyz if isinstance(ctx_xyz, (list, tuple)) else [ctx_xyz]
-            preds = head.forward_multi(noisy, trajectory_mask, timesteps.to(dev), toks, xyzs, instruction, cg, gg,
+            preds = head.forward_multi(noisy, trajectory_mask, timesteps.to(dev), _as_list(tokens), _as_list(ctx_xyz), instruction, cg, gg,
                                        head.begin_dropout if (head.training and head.dropout_p > 0) else None)
             loss = sum(O.ElemLossFn.apply(p_[..., :3], gt[..., :3], 1, 100.0) + O.ElemLossFn.apply(p_[..., 3:9], gt[..., 3:9], 1, 10.0)
                        for p_ in preds)
@@ -1015,54 +1048,49 @@ class DiffusionPlanner(nn.Module):
             if step_noise is not None and step_noise.shape[0] != K:
                 raise ValueError("step_noise has %d leading rows for a schedule of %d steps (one row per step position)"
                                  % (step_noise.shape[0], K))
+        D = curr_gripper.shape[-1] + 2
         if G is not None:
-            check_candidate_noise(init_noise, step_noise, B, G, Ln, curr_gripper.shape[-1] + 2, K if scheduled else self.n_steps)
+            check_candidate_noise(init_noise, step_noise, B, G, Ln, D, K if scheduled else self.n_steps)
+
+        # ---- the plan: which launches serve the call, from the shapes and the CU count alone
         multi = head.attn_rounds * head.feat_scales > 1
+        plan = sampler_plan(B, G, Ln, D, head.curr_gripper_embed.weight.shape[1], head.num_attn_heads, self.n_steps,
+                            torch.cuda.get_device_properties(dev).multi_processor_count, multi, fused, num_inference_steps, scheduler,
+                            eta, n_steps)
+        group = plan.group
         tb = self.tables(dev)
-        # candidate groups: the persistent sampler on the per-scene cache.  Decided on the host from the shapes alone, by the
-        # conditions that select the fused path and the persistent sampler below.
-        E_ = head.curr_gripper_embed.weight.shape[1]
-        D_ = curr_gripper.shape[-1] + 2
-        group = (G is not None and not multi and (FUSED_DENOISE if fused is None else fused) and DN_PERSIST and E_ <= 128 and
-                 D_ <= 16 and min(Ln, 16) * D_ <= 160 and Ln <= 64 and head.persist_fits(B * G, Ln, dev))
-        flip_noise = False
-        if group and not scheduled:
-            # a3d_dn_persist_group addresses its tables by step position: the full chain is the K = T "ddpm" schedule (the same
-            # coefficients and AdaLN rows, bit for bit), with the noise of timestep t at row T - 1 - t
-            scheduled, K, flip_noise = True, self.n_steps, True
-        sched = self.schedule(dev, K, scheduler, eta) if scheduled else None
+        sched = self.schedule(dev, plan.K, scheduler, eta) if plan.scheduled else None
+        # tables of the DDPM-step kernels and of the AdaLN modulation: by timestep (full chain) or by step position (schedule)
+        tables, time_sin = (tb, self._time_tables["sin"]) if sched is None else (sched, sched.time_sin)
+
+        # ---- conditioning and candidate expansion
         tokens, ctx_xyz, cg, gg = self._prepare(rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens,
                                                 signals=not fused_conditioning)
+        tokens, ctx_xyz = _as_list(tokens), _as_list(ctx_xyz)      # one entry per scale
         if fused_conditioning:
             # every per-trajectory conditioning tensor at once, before the candidate expansion below (the kernel expands itself)
             Gk = 1 if G is None else G
             if init_noise is None:
-                init_noise = torch.randn((B * Gk, Ln, D_), device=dev)
+                init_noise = torch.randn((B * Gk, Ln, D), device=dev)
             else:
                 init_noise = init_noise.to(dev).float().reshape(B * Gk, Ln, -1)
             cg, gg, cond_data, cond_mask_u8, kmask, traj = traj_condition(
                 curr_gripper, goal_gripper, self.gripper_loc_bounds, trajectory_mask, init_noise, Gk, self._use_goal_at_test)
         B_scene = B
         if G is not None:
-            rows = self.n_steps if (sched is None or flip_noise) else sched.K
             if init_noise is not None:
                 init_noise = init_noise.reshape(B * G, Ln, -1)
             if step_noise is not None:
-                step_noise = step_noise.reshape(rows, B * G, Ln, -1)
-                if flip_noise:
+                step_noise = step_noise.reshape(step_noise.shape[0], B * G, Ln, -1)
+                if plan.flip_noise:
                     step_noise = step_noise.flip(0)
             if not group:
                 # fallback paths: every scene's inputs G times along the batch axis (after the image encoding, which stays per scene)
                 rep_ = lambda x: None if x is None else x.repeat_interleave(G, 0)
-                tokens = [rep_(x) for x in tokens] if isinstance(tokens, (list, tuple)) else rep_(tokens)
-                ctx_xyz = [rep_(x) for x in ctx_xyz] if isinstance(ctx_xyz, (list, tuple)) else rep_(ctx_xyz)
+                tokens, ctx_xyz = [rep_(x) for x in tokens], [rep_(x) for x in ctx_xyz]
                 cg, gg, instruction, trajectory_mask = rep_(cg), rep_(gg), rep_(instruction), rep_(trajectory_mask)
                 B = B * G
-        if not multi:
-            ctx, ctx_xyz, instr = head.encode_context(tokens, ctx_xyz, instruction, cg, gg)
-        # conditioning: start pose at index 0, goal at L - pad - 1 and after (no host sync: index arithmetic on device)
-        D = cg.shape[-1]
-        E = head.curr_gripper_embed.weight.shape[1]
+        # start pose at index 0, goal at L - pad - 1 and after (no host sync: index arithmetic on device)
         if not fused_conditioning:
             ar = torch.arange(Ln, device=dev)[None, :]
             cond_mask = (ar == 0)
@@ -1088,11 +1116,6 @@ class DiffusionPlanner(nn.Module):
             if step_noise is None:
                 step_noise = torch.randn((self.n_steps if sched is None else sched.K, B, Ln, D), device=dev)
             step_noise = step_noise.to(dev).float().contiguous()
-        steps = list(range(self.n_steps - 1, -1, -1)) if sched is None else list(sched.timesteps)
-        if n_steps is not None:
-            steps = steps[:n_steps]
-        # tables of the DDPM-step kernels and of the AdaLN modulation: by timestep (full chain) or by step position (schedule)
-        time_sin = self._time_tables["sin"] if sched is None else sched.time_sin
         sched_key = None if sched is None else sched.key
         if G is not None:
             sched_key = (sched_key, "num_samples", G, "group" if group else "expanded")
@@ -1100,132 +1123,71 @@ class DiffusionPlanner(nn.Module):
             sched_key = (sched_key, "fused_conditioning")
         else:
             traj = (init_noise.to(dev).float() + cond_data).contiguous()
-        trace = []
-        # fused per-step kernels (csrc/denoise.hip) whenever the trajectory fits one 16-row tile; else the op-by-op path
-        fused = FUSED_DENOISE if fused is None else fused
-        # fused kernels (csrc/denoise.hip): per-phase launches serve one 16-row tile; the persistent sampler up to four (L <= 64: the
-        # reference's interpolation_length = 50, scripts/train_trajectory.sh:7-8, online_evaluation/eval.sh:17)
-        fused = fused and E <= 128 and D <= 16 and min(Ln, 16) * D <= 160 and not multi and (Ln <= 16 or (DN_PERSIST and Ln <= 64))
+
+        # ---- step-invariant state of the planned path; `static` is what a captured graph refreshes in place
         if multi:
-            # multi-round / multi-scale heads: the fine-scale context follows the previous prediction, so nothing but the
-            # image encoding is step-invariant -- every step evaluates the full head (no K/V cache, no fused kernels)
-            toks = tokens if isinstance(tokens, (list, tuple)) else [tokens]
-            xyzs = ctx_xyz if isinstance(ctx_xyz, (list, tuple)) else [ctx_xyz]
-            state, static = None, list(toks) + list(xyzs) + [instruction, cg, gg]
+            # the fine-scale context follows the previous prediction, so nothing but the image encoding is step-invariant: every
+            # step evaluates the full head (no K/V cache, no fused kernels)
+            state, static = None, tokens + ctx_xyz + [instruction, cg, gg]
             tmask = trajectory_mask.bool()
-        elif fused:
-            # a replay of the captured loop addresses the state retained in self._graph: skip building a second set of persistent-
-            # sampler buffers (a ctypes table, a pageable host-to-device copy = a host sync, five allocations) that would be thrown away
-            gr_ = self._graph
-            reuse = (use_graph and not return_trace and gr_ is not None and gr_["key"][:3] == (B, Ln, tuple(steps)) and
-                     gr_["key"][-1] == sched_key and isinstance(gr_.get("state"), dict) and gr_["state"].get("persist") is not None)
-            state = head.build_fused(ctx, ctx_xyz, instr, kmask, time_sin, Ln, with_persist=not reuse, n_cand=G if group else 1)
-            if reuse:
-                state["persist"] = gr_["state"]["persist"]
-            elif group and state["persist"] is not None:
-                state["persist"]["group"] = True
-            static = list(state["tensors"])
-            if Ln > 16 and state.get("persist") is None:           # too many units for the CU count: the op-by-op path serves it
-                fused = False
-                state = head.build_kv_cache(ctx, ctx_xyz, instr)
+        else:
+            ctx, cxyz, instr = head.encode_context(tokens[0], ctx_xyz[0], instruction, cg, gg)
+            if plan.path == "op-by-op":
+                state = head.build_kv_cache(ctx, cxyz, instr)
                 static = [c[k] for c in state["ctx"] for k in ("Ks", "Vt")] + \
                     ([state["lang"]["Ks"], state["lang"]["Vt"]] if "lang" in state else [])
-        else:
-            state = head.build_kv_cache(ctx, ctx_xyz, instr)
-            static = [c[k] for c in state["ctx"] for k in ("Ks", "Vt")] + \
-                ([state["lang"]["Ks"], state["lang"]["Vt"]] if "lang" in state else [])
+            else:
+                # fused kernels (csrc/denoise.hip); the persistent sampler's own state follows below, once the graph key is known
+                state = head.build_fused(ctx, cxyz, instr, kmask, time_sin, Ln, n_cand=G if group else 1)
+                static = list(state["tensors"])
         static = static + ([] if step_noise is None else [step_noise]) + [cond_data, cond_mask_u8, kmask]
         if sched is not None:
             static = static + [sched.coef_pos, sched.coef_rot]
-
-        # the persistent sampler walks its tables row by row: consecutive timesteps of the full chain, or any schedule by position
-        in_order = sched is not None or all(a_ - b_ == 1 for a_, b_ in zip(steps, steps[1:]))
-        persist = fused and state.get("persist") is not None and in_order
-        if group and not persist:
+        key = (B, Ln, plan.steps, plan.path, tuple((tuple(t_.shape), t_.dtype) for t_ in static), sched_key)
+        replay = use_graph and not return_trace
+        if plan.path == "persistent":
+            # a replay of the captured loop addresses the state retained in self._graph: no second set of persistent-sampler buffers
+            # (a ctypes table, a pageable host-to-device copy = a host sync, five allocations) that would be thrown away
+            gr = self._graph
+            state["persist"] = gr["state"]["persist"] if (replay and gr is not None and gr["key"] == key) else \
+                head._build_persist(state, B, Ln, time_sin.shape[0], group)
+        if group and state.get("persist") is None:
             raise RuntimeError("num_samples: the per-scene cache was built for a3d_dn_persist_group, which cannot serve this call")
         if G is not None:
             self._last_state = state                        # tests read the leading dimensions of the cache
-        # which sampler serves this call (read by the bench line and the tests)
-        self.last_sampler_path = "multi-round" if multi else (
-            ("persistent (a3d_dn_persist_group)" if group else
-             "persistent (a3d_dn_persist)" if sched is None else "persistent (a3d_dn_persist_sched)") if persist else
-            ("per-phase fused launches" if fused else "op-by-op"))
+        self.last_sampler_path = plan.label                 # which sampler serves this call (read by the bench line and the tests)
+        trace = []
 
-        def run_scheduled(x):
-            # step position i is the row of every table; the step at timestep 0 (position K - 1) is terminal
-            if persist and not return_trace:
-                return head.fused_persist(state, x, 0, len(steps), step_noise, cond_data, cond_mask_u8, sched, sched=sched)
-            for i, t in enumerate(steps):
-                term = i == sched.K - 1
-                nz = None if (step_noise is None or term) else step_noise[i]
-                if multi:
-                    tt = torch.full((B,), t, device=dev, dtype=torch.long)
-                    out = head.forward_multi(x, tmask, tt, toks, xyzs, instruction, cg, gg)[-1]
-                    x = O.ddpm_step_sched(out, x, nz, cond_data, cond_mask_u8, sched.coef_pos, sched.coef_rot, i, term)
-                elif persist:
-                    x = head.fused_persist(state, x, i, 1, step_noise, cond_data, cond_mask_u8, sched, sched=sched)
-                elif fused:
-                    x = head.fused_step(state, x, i, nz, cond_data, cond_mask_u8, sched, terminal=term)
+        def run(x):
+            if plan.path == "persistent" and not return_trace:      # the whole loop: one launch
+                return head.fused_persist(state, x, 0 if plan.scheduled else plan.steps[0], len(plan.steps), step_noise, cond_data,
+                                          cond_mask_u8, tables)
+            for i, t in enumerate(plan.steps):
+                # a schedule addresses its tables and its noise by step POSITION and names its terminal step (timestep 0, position
+                # K - 1); the full chain addresses them by timestep.  No step at timestep 0 reads noise.
+                row, term = (i, t == 0) if plan.scheduled else (t, None)
+                nz = None if (step_noise is None or t == 0) else step_noise[row]
+                if plan.path == "persistent":               # traced: the same kernel, one step per launch
+                    x = head.fused_persist(state, x, row, 1, step_noise, cond_data, cond_mask_u8, tables)
+                elif plan.path == "per-phase":
+                    x = head.fused_step(state, x, row, nz, cond_data, cond_mask_u8, tables)
                 else:
-                    out = head.denoise_tokens_cached(x, kmask, t, state, self._time_tables)
-                    x = O.ddpm_step_sched(out, x, nz, cond_data, cond_mask_u8, sched.coef_pos, sched.coef_rot, i, term)
+                    if multi:
+                        tt = torch.full((B,), t, device=dev, dtype=torch.long)
+                        out = head.forward_multi(x, tmask, tt, tokens, ctx_xyz, instruction, cg, gg)[-1]
+                    else:
+                        out = head.denoise_tokens_cached(x, kmask, t, state, self._time_tables)
+                    if term is None:
+                        x = O.ddpm_step(out, x, nz, cond_data, cond_mask_u8, tables.coef_pos, tables.coef_rot, row)
+                    else:
+                        x = O.ddpm_step_sched(out, x, nz, cond_data, cond_mask_u8, tables.coef_pos, tables.coef_rot, row, term)
                 if return_trace:
                     trace.append(x)
             return x
 
-        def run_loop(x):
-            if sched is not None:
-                return run_scheduled(x)
-            if persist and not return_trace:                # the whole loop: one launch
-                return head.fused_persist(state, x, steps[0], len(steps), step_noise, cond_data, cond_mask_u8, tb)
-            for t in steps:
-                nz = step_noise[t] if t > 0 else None
-                if multi:
-                    tt = torch.full((B,), t, device=dev, dtype=torch.long)
-                    out = head.forward_multi(x, tmask, tt, toks, xyzs, instruction, cg, gg)[-1]
-                    x = O.ddpm_step(out, x, nz, cond_data, cond_mask_u8, tb.coef_pos, tb.coef_rot, t)
-                elif persist:                              # traced: the same kernel, one step per launch
-                    x = head.fused_persist(state, x, t, 1, step_noise, cond_data, cond_mask_u8, tb)
-                elif fused:
-                    x = head.fused_step(state, x, t, nz, cond_data, cond_mask_u8, tb)
-                else:
-                    out = head.denoise_tokens_cached(x, kmask, t, state, self._time_tables)
-                    x = O.ddpm_step(out, x, nz, cond_data, cond_mask_u8, tb.coef_pos, tb.coef_rot, t)
-                if return_trace:
-                    trace.append(x)
-            return x
+        traj = self._replay(key, run, traj, static, state) if replay else run(traj)
 
-        if use_graph and not return_trace:
-            key = (B, Ln, tuple(steps), fused, tuple((tuple(t_.shape), t_.dtype) for t_ in static), sched_key)
-            if self._graph is not None and self._graph["key"] != key and fused and state.get("persist") is self._graph["state"].get("persist"):
-                # the shapes changed after all (another context size): this call needs its own persistent-sampler state
-                state["persist"] = head._build_persist(state, B, Ln, head.num_attn_heads, E, state["Sp"], time_sin.shape[0], dev) if DN_PERSIST else None
-                if group and state["persist"] is not None:
-                    state["persist"]["group"] = True
-                persist = fused and state.get("persist") is not None and in_order
-            if self._graph is None or self._graph["key"] != key:
-                static_in = traj.clone()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    run_loop(static_in)                     # warm-up (allocator, lazy module state) outside capture
-                torch.cuda.current_stream().wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                # "state" keeps every buffer the captured launches address alive (workspaces, the persistent sampler's tables)
-                self._graph = {"key": key, "in": static_in, "static": static, "state": state}
-                with torch.cuda.graph(g):
-                    self._graph["out"] = run_loop(static_in)
-                self._graph["g"] = g
-            gr = self._graph
-            # refresh the captured buffers in place (same addresses; the key pins every shape and dtype)
-            gr["in"].copy_(traj)
-            for dst, src in zip(gr["static"], static):
-                if dst is not src:
-                    dst.copy_(src)
-            gr["g"].replay()
-            traj = gr["out"]
-        else:
-            traj = run_loop(traj)
+        # ---- poses, candidates, ranking
         final = signal_to_pose(traj, self.gripper_loc_bounds)
         if G is not None:
             final = final.reshape(B_scene, G, Ln, final.shape[-1])
@@ -1235,3 +1197,28 @@ class DiffusionPlanner(nn.Module):
             self.last_ranking = PlannerRanking(*rk, candidates=final)
             final = rk.selected
         return (final, trace) if return_trace else final
+
+    def _replay(self, key, run, traj, static, state):
+        """run(traj) through a captured graph: captured on the first call with this key (shapes, steps, path, schedule), afterwards
+        the captured buffers are refreshed in place and the graph is replayed."""
+        if self._graph is None or self._graph["key"] != key:
+            static_in = traj.clone()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                run(static_in)                              # warm-up (allocator, lazy module state) outside capture
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            # "state" keeps every buffer the captured launches address alive (workspaces, the persistent sampler's tables)
+            self._graph = {"key": key, "in": static_in, "static": static, "state": state}
+            with torch.cuda.graph(g):
+                self._graph["out"] = run(static_in)
+            self._graph["g"] = g
+        gr = self._graph
+        # refresh the captured buffers in place (same addresses; the key pins every shape and dtype)
+        gr["in"].copy_(traj)
+        for dst, src in zip(gr["static"], static):
+            if dst is not src:
+                dst.copy_(src)
+        gr["g"].replay()
+        return gr["out"]

@@ -10,6 +10,7 @@ c0 = sqrt(a_prev) - c1 sqrt(a_t), c2 = sigma; the step at t = 0 returns the in-p
 import math
 import os
 import sys
+from collections import Counter
 
 import pytest
 import torch
@@ -342,3 +343,75 @@ def test_multi_round_head_scheduled_vs_oracle(a3d, dev):
         scale_close(f"{tag} sampled xyz vs oracle", f[..., :3], ofinal[..., :3], 3e-4)
         sign = torch.sign((f[..., 3:] * ofinal[..., 3:]).sum(-1, keepdim=True))
         scale_close(f"{tag} sampled quaternion vs oracle", f[..., 3:] * sign, ofinal[..., 3:], 3e-4)
+
+
+# ------------------------------------------------------------------------------------------------ launch census
+# Launches of ONE op-by-op denoise step of the `planner` head (trajectory encoder, instruction layer, eight attention layers, the two
+# regressors, the DDPM step), recorded with the wrapper below at ea60aa8, the commit before sampler_plan; the same at L = 8 and L = 20.
+OP_BY_OP_LAUNCHES_PER_STEP = 189
+N_LAYERS = 8                                                # 4 shared + 2 position + 2 rotation layers of num_query_cross_attn_layers = 6
+
+CENSUS = [  # name, Ln, G, DN_PERSIST, fused, path
+    ("persistent", 8, None, True, None, "persistent (a3d_dn_persist)"),
+    ("persistent, two row tiles", 20, None, True, None, "persistent (a3d_dn_persist)"),
+    ("candidate group", 8, 2, True, None, "persistent (a3d_dn_persist_group)"),
+    ("per-phase", 8, None, False, None, "per-phase fused launches"),
+    ("op-by-op", 8, None, True, False, "op-by-op"),
+    ("op-by-op, L = 20 without the persistent sampler", 20, None, False, None, "op-by-op"),
+    ("op-by-op, L = 20 with too many trajectories for the CUs", 20, None, True, None, "op-by-op"),
+]
+
+
+def launches(m, a3d, d, tdev, persist, **kw):
+    """Entry names of one eager compute_trajectory call, in launch order (lib.call wrapped as in test_act3d_gpu.py)."""
+    D = a3d.diffusion
+    seen, call, keep = [], a3d.lib.call, D.DN_PERSIST
+    D.DN_PERSIST = persist
+    a3d.ops.L.call = lambda entry, *args: (seen.append(entry), call(entry, *args))[1]
+    try:
+        m.compute_trajectory(d["mask"], None, d["pcd"], d["instr"], d["curr_gripper"], d["goal_gripper"], visual_tokens=tdev, **kw)
+    finally:
+        a3d.ops.L.call = call
+        D.DN_PERSIST = keep
+    return seen
+
+
+@pytest.mark.parametrize("name,Ln,G,persist,fused,path", CENSUS, ids=[c[0] for c in CENSUS])
+def test_launch_census_of_every_sampler_path(planner, dev, a3d, name, Ln, G, persist, fused, path):
+    """Which entry points two eager steps of compute_trajectory launch, per path: the persistent sampler is ONE launch for the loop,
+    the per-phase path 1 + 2 * layers + 1 per step, the op-by-op path no a3d_dn_* launch and the recorded count per step.  A call the
+    plan sends to the op-by-op path builds no fused state first: it launches what the fused=False call launches."""
+    m, _ = planner
+    n = 2
+    B = 2
+    if "too many" in name:                                  # 2 * B * ceil(L / 16) + 16 one above the CU count
+        B = (torch.cuda.get_device_properties(dev).multi_processor_count - 16) // 4 + 1
+    inp, tokens, d, tdev = inputs(dev, 99, B, Ln, 2)
+    seen = launches(m, a3d, d, tdev, persist, n_steps=n, fused=fused, num_samples=G)
+    assert m.last_sampler_path == path
+    dn = [e for e in seen if e.startswith("a3d_dn_")]
+    print(f"[census] {name}: {len(seen)} launches in the call, a3d_dn_*: {sorted(set(dn))}, "
+          f"a3d_proj_rope_split16: {seen.count('a3d_proj_rope_split16')}")
+    if path.startswith("persistent"):
+        assert dn == [path[path.index("(") + 1:-1]], dn
+        assert abort_word(m) == 0
+    elif path.startswith("per-phase"):
+        per_step = {"a3d_dn_head": 1, "a3d_dn_cross": N_LAYERS, "a3d_dn_rest": N_LAYERS, "a3d_dn_tail": 1}
+        assert sum(per_step.values()) == 1 + 2 * N_LAYERS + 1 == 18
+        assert {e: dn.count(e) for e in set(dn)} == {e: n * c for e, c in per_step.items()}, dn
+        first, last = seen.index("a3d_dn_head"), len(seen) - 1 - seen[::-1].index("a3d_dn_tail")
+        assert last + 1 - first == n * 18, "other launches inside the step loop: %s" % seen[first:last + 1]
+    else:
+        assert not dn, dn
+        ends = [i for i, e in enumerate(seen) if e == "a3d_ddpm_step"]
+        assert len(ends) == n
+        per_step = ends[1] - ends[0]
+        steps = [seen[i + 1 - per_step:i + 1] for i in ends]
+        print(f"[census] {name}: {per_step} launches per step")
+        assert ends[0] + 1 - per_step >= 0 and steps[0] == steps[1]
+        assert per_step == OP_BY_OP_LAUNCHES_PER_STEP
+        if Ln > 16:
+            # the op-by-op path launches a3d_proj_rope_split16 itself (encode_context, the self-attention operands), so "none of
+            # build_fused's" is held against the fused=False call: the same launches in the same order, before the loop and in it
+            ref = launches(m, a3d, d, tdev, persist, n_steps=n, fused=False)
+            assert seen == ref, "a fused state was built for a call the op-by-op path serves: %s" % dict(Counter(seen) - Counter(ref))
