@@ -18,9 +18,10 @@ import random
 
 import torch
 
-from .diffusion import RANK_MAX_CANDIDATES, check_num_samples, check_rot_weight, check_select
+from .diffusion import RANK_MAX_CANDIDATES, check_scene, check_clearance_args, check_num_samples, check_rot_weight, check_scene_select
 
-_TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight")
+_TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight",
+            "scene_mask", "clear_margin", "clear_skip")
 
 
 def _same_tensors(a, b):
@@ -245,7 +246,8 @@ class Actioner:
         (B, history, >= action_dim), read only with predict_keypose=False; trajectory_mask (B, L), needed with
         predict_trajectory=True.  Returns {"action": (B, 8) or gt_action[:, -1], "trajectory": compute_trajectory's result or None,
         "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps, select,
-        rot_weight) go to compute_trajectory unchanged; with select the candidates are ranked on the device, "trajectory" is the
+        rot_weight, scene_mask, clear_margin, clear_skip) go to compute_trajectory unchanged (a rule that weighs "clearance" scores the
+        candidates against pcds[:, -1]); with select the candidates are ranked on the device, "trajectory" is the
         selected one (B, L, 8) and self.last_ranking mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
         and the sampling loop as graphs."""
         bad = [k for k in sample_kw if k not in _TRAJ_KW]
@@ -260,8 +262,13 @@ class Actioner:
             if check_num_samples(sample_kw["num_samples"]) > RANK_MAX_CANDIDATES:
                 raise ValueError("select serves at most %d candidates per scene, num_samples is %d" % (
                     RANK_MAX_CANDIDATES, sample_kw["num_samples"]))
-            check_select(sample_kw["select"], True, True)
+            _, w_clear = check_scene_select(sample_kw["select"], True, True, True)
             check_rot_weight(sample_kw.get("rot_weight", 1.0))
+            if w_clear != 0.0:
+                if not torch.is_tensor(pcds) or pcds.dim() != 6:
+                    raise ValueError("pcds must be (B, history, cameras, 3, H, W)")
+                check_scene(pcds[:, -1], sample_kw.get("scene_mask"), pcds.shape[0])
+                check_clearance_args(sample_kw.get("clear_margin", 0.05), sample_kw.get("clear_skip", (1, 1)))
         self._check(rgbs, pcds, gripper, gt_action, trajectory_mask, use_graph, ghost_points)
         share = self._sharing()
         output = {"action": None, "attention": {}}

@@ -10,6 +10,8 @@
 //   smooth     mean over valid triples (i-1, i, i+1) of |(p_{i+1} - p_i) - (p_i - p_{i-1})|^2
 //   length     sum over valid pairs (i, i+1) of |p_{i+1} - p_i|_2
 //   bounds     (valid rows with a coordinate outside [lo, hi]) / max(n, 1)
+// a3d_traj_rank_extra adds one more term, computed by another launch (the scene clearance of csrc/traj_clearance.hip): extra[b][g],
+// weighed by w_extra and added to the score LAST, when and only when w_extra != 0; terms stays [G][5].
 // rho(q, r) = 1 - <q, r>^2 for unit quaternions, evaluated by Lagrange's identity as sum_{i<j} (q_i r_j - q_j r_i)^2: the same
 // number, an exact 0 for bit-identical rows (no cancellation against 1), relative instead of absolute accuracy near identical rotations.
 //
@@ -96,8 +98,9 @@ struct TrajRankArgs {
   float* scores;                 // [B][G] or NULL
   float* terms;                  // [B][G][5] or NULL
   float* selected;               // [B][L][Dp] or NULL
+  const float* extra;            // [B][G] or NULL: a term computed elsewhere (a3d_traj_rank_extra), added last with weight w_extra
   float w[5];
-  float rot_weight;
+  float rot_weight, w_extra;
   int ldg, G, L, Dp, cstride;
 };
 
@@ -230,6 +233,7 @@ __global__ __launch_bounds__(TR_THREADS) void traj_rank_kernel(const TrajRankArg
       float s = 0.f;
 #pragma unroll
       for (int k = 0; k < 5; ++k) { tbuf[g * 5 + k] = t[k]; s += a.w[k] * t[k]; }
+      if (a.w_extra != 0.f) s += a.w_extra * a.extra[(size_t)b * G + g];   // only when weighed: 0 * NaN would spoil the score
       sc[g] = fabsf(s) <= FLT_MAX ? s : INFINITY;          // NaN and +-inf rank last
     }
   }
@@ -261,27 +265,29 @@ __global__ __launch_bounds__(TR_THREADS) void traj_rank_kernel(const TrajRankArg
 
 using namespace a3d;
 
-extern "C" int a3d_traj_rank(const float* poses, const unsigned char* tmask, const float* goal, int ldg, const float* bounds,
-                             float w_consensus, float w_goal, float w_smooth, float w_length, float w_bounds, float rot_weight,
-                             int* best, int* order, float* scores, float* terms, float* selected, int B, int G, int L, int Dp,
-                             void* stream) {
-  if (!poses || !tmask || !best) { set_error("a3d_traj_rank: null pointer (poses, tmask and best are required)"); return A3D_ERR_ARG; }
-  if (B <= 0 || G <= 0 || L <= 0) { set_error("a3d_traj_rank: B, G and L must be positive (B=%d G=%d L=%d)", B, G, L); return A3D_ERR_ARG; }
-  if (G > TR_MAX_G) { set_error("a3d_traj_rank: G=%d exceeds %d candidates per scene", G, TR_MAX_G); return A3D_ERR_ARG; }
-  if (Dp != 7 && Dp != 8) { set_error("a3d_traj_rank: Dp=%d, pose rows have 7 or 8 channels", Dp); return A3D_ERR_ARG; }
-  if (goal && ldg < 7) { set_error("a3d_traj_rank: goal leading dimension %d is below 7", ldg); return A3D_ERR_ARG; }
+static int traj_rank_launch(const char* me, const float* poses, const unsigned char* tmask, const float* goal, int ldg,
+                            const float* bounds, float w_consensus, float w_goal, float w_smooth, float w_length, float w_bounds,
+                            float rot_weight, int* best, int* order, float* scores, float* terms, float* selected, int B, int G, int L,
+                            int Dp, const float* extra, float w_extra, void* stream) {
+  if (!poses || !tmask || !best) { set_error("%s: null pointer (poses, tmask and best are required)", me); return A3D_ERR_ARG; }
+  if (B <= 0 || G <= 0 || L <= 0) { set_error("%s: B, G and L must be positive (B=%d G=%d L=%d)", me, B, G, L); return A3D_ERR_ARG; }
+  if (G > TR_MAX_G) { set_error("%s: G=%d exceeds %d candidates per scene", me, G, TR_MAX_G); return A3D_ERR_ARG; }
+  if (Dp != 7 && Dp != 8) { set_error("%s: Dp=%d, pose rows have 7 or 8 channels", me, Dp); return A3D_ERR_ARG; }
+  if (goal && ldg < 7) { set_error("%s: goal leading dimension %d is below 7", me, ldg); return A3D_ERR_ARG; }
   const float w[5] = {w_consensus, w_goal, w_smooth, w_length, w_bounds};
   for (int k = 0; k < 5; ++k)
-    if (!(w[k] >= 0.f && w[k] <= FLT_MAX)) { set_error("a3d_traj_rank: weight %d is negative or not finite", k); return A3D_ERR_ARG; }
-  if (!(fabsf(rot_weight) <= FLT_MAX)) { set_error("a3d_traj_rank: rot_weight is not finite"); return A3D_ERR_ARG; }
-  if (w_goal != 0.f && !goal) { set_error("a3d_traj_rank: a goal weight without a goal"); return A3D_ERR_ARG; }
-  if (w_bounds != 0.f && !bounds) { set_error("a3d_traj_rank: a bounds weight without bounds"); return A3D_ERR_ARG; }
-  if ((long long)G * L * 8 > 0x7fffffffLL) { set_error("a3d_traj_rank: G * L * 8 overflows int (G=%d L=%d)", G, L); return A3D_ERR_ARG; }
+    if (!(w[k] >= 0.f && w[k] <= FLT_MAX)) { set_error("%s: weight %d is negative or not finite", me, k); return A3D_ERR_ARG; }
+  if (!(fabsf(rot_weight) <= FLT_MAX)) { set_error("%s: rot_weight is not finite", me); return A3D_ERR_ARG; }
+  if (w_goal != 0.f && !goal) { set_error("%s: a goal weight without a goal", me); return A3D_ERR_ARG; }
+  if (!(w_extra >= 0.f && w_extra <= FLT_MAX)) { set_error("%s: the extra weight is negative or not finite", me); return A3D_ERR_ARG; }
+  if (w_extra != 0.f && !extra) { set_error("%s: an extra weight without an extra term", me); return A3D_ERR_ARG; }
+  if (w_bounds != 0.f && !bounds) { set_error("%s: a bounds weight without bounds", me); return A3D_ERR_ARG; }
+  if ((long long)G * L * 8 > 0x7fffffffLL) { set_error("%s: G * L * 8 overflows int (G=%d L=%d)", me, G, L); return A3D_ERR_ARG; }
   TrajRankArgs a;
   a.poses = poses; a.tmask = tmask; a.goal = goal; a.bounds = bounds;
   a.best = best; a.order = order; a.scores = scores; a.terms = terms; a.selected = selected;
   for (int k = 0; k < 5; ++k) a.w[k] = w[k];
-  a.rot_weight = rot_weight;
+  a.rot_weight = rot_weight; a.extra = extra; a.w_extra = w_extra;
   a.ldg = goal ? ldg : 0; a.G = G; a.L = L; a.Dp = Dp;
   a.cstride = (7 * L) | 1;
   const size_t fixed = ((size_t)G * G + (size_t)G * 6 + 16) * sizeof(float);
@@ -293,5 +299,21 @@ extern "C" int a3d_traj_rank(const float* poses, const unsigned char* tmask, con
   } else {
     hipLaunchKernelGGL(traj_rank_kernel<false>, dim3(B), dim3(TR_THREADS), fixed, (hipStream_t)stream, a);
   }
-  return check_launch("a3d_traj_rank");
+  return check_launch(me);
+}
+
+extern "C" int a3d_traj_rank(const float* poses, const unsigned char* tmask, const float* goal, int ldg, const float* bounds,
+                             float w_consensus, float w_goal, float w_smooth, float w_length, float w_bounds, float rot_weight,
+                             int* best, int* order, float* scores, float* terms, float* selected, int B, int G, int L, int Dp,
+                             void* stream) {
+  return traj_rank_launch("a3d_traj_rank", poses, tmask, goal, ldg, bounds, w_consensus, w_goal, w_smooth, w_length, w_bounds,
+                          rot_weight, best, order, scores, terms, selected, B, G, L, Dp, nullptr, 0.f, stream);
+}
+
+extern "C" int a3d_traj_rank_extra(const float* poses, const unsigned char* tmask, const float* goal, int ldg, const float* bounds,
+                                   float w_consensus, float w_goal, float w_smooth, float w_length, float w_bounds, float rot_weight,
+                                   int* best, int* order, float* scores, float* terms, float* selected, int B, int G, int L, int Dp,
+                                   const float* extra, float w_extra, void* stream) {
+  return traj_rank_launch("a3d_traj_rank_extra", poses, tmask, goal, ldg, bounds, w_consensus, w_goal, w_smooth, w_length, w_bounds,
+                          rot_weight, best, order, scores, terms, selected, B, G, L, Dp, extra, w_extra, stream);
 }

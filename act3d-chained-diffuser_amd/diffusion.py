@@ -17,7 +17,9 @@ Additive keyword arguments: `noise`, `timesteps` (training) and `init_noise`, `s
 draws; `visual_tokens` bypasses the backbone + FPN; `num_inference_steps` / `scheduler` / `eta` select a few-step sampler
 schedule; `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8);
 `fused_conditioning=True` builds the sampler's conditioning tensors in one launch (a3d_traj_condition); `select` / `rot_weight`
-rank the candidates on the device and return the selected trajectory (rank_trajectories, a3d_traj_rank).  Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
+rank the candidates on the device and return the selected trajectory (rank_trajectories, a3d_traj_rank), optionally against the
+observed point cloud (trajectory_clearance, a3d_traj_clearance: the "clearance" term of a select rule).
+Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
 attention weights, residual branches, FFN -- and in the traj_encoder / regressor MLPs: layers.py:10,
 diffusion_head.py:46,183,193) runs on a device-resident Philox stream (csrc/dropout.hip, attention kernels): same
 distribution as the reference's torch generator, not the same draws.  The additive constructor keyword `dropout`
@@ -222,12 +224,23 @@ RANK_MAX_CANDIDATES = 64
 TrajectoryRanking = collections.namedtuple("TrajectoryRanking", ("best", "order", "scores", "terms", "selected"))
 # what compute_trajectory(select=...) keeps on the planner: the ranking and all candidates (B, G, L, 8)
 PlannerRanking = collections.namedtuple("PlannerRanking", TrajectoryRanking._fields + ("candidates",))
+# the scene-aware term (csrc/traj_clearance.hip): weighed by select={"clearance": w} or the preset "clear", never part of RANK_TERMS
+CLEARANCE_TERM = "clearance"
+CLEARANCE_PRESET = "clear"
+TrajectoryClearance = collections.namedtuple("TrajectoryClearance", ("nearest", "clearance"))
+# what rank_trajectories returns when the rule weighs the clearance term: the five fields in order, then clearance (B, G), nearest (B, G, L)
+SceneTrajectoryRanking = collections.namedtuple("SceneTrajectoryRanking", TrajectoryRanking._fields + ("clearance", "nearest"))
+ScenePlannerRanking = collections.namedtuple("ScenePlannerRanking", SceneTrajectoryRanking._fields + ("candidates",))
 
 
 def check_select(select, have_goal=True, have_bounds=True):
     """Validates a `select` rule on the host and returns its five weights in RANK_TERMS order.  A preset name ("consensus", "goal",
     "smooth", "shortest") puts weight 1 on one term; a dict maps a subset of RANK_TERMS to finite, non-negative weights, not all zero.
     A non-zero goal / bounds weight needs a goal / bounds."""
+    return _term_weights(select, have_goal, have_bounds, False)
+
+
+def _term_weights(select, have_goal, have_bounds, all_zero_ok):
     if isinstance(select, str):
         if select not in RANK_PRESETS:
             raise ValueError("select=%r: the presets are %s (or a dict over %s)" % (select, sorted(RANK_PRESETS), list(RANK_TERMS)))
@@ -243,7 +256,7 @@ def check_select(select, have_goal=True, have_bounds=True):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
             raise ValueError("select[%r] = %r: a weight is a finite, non-negative number" % (k, v))
         w.append(float(v))
-    if not any(w):
+    if not any(w) and not all_zero_ok:
         raise ValueError("select gives every term weight 0")
     if w[1] != 0.0 and not have_goal:
         raise ValueError("select weighs the goal term, but no goal is given")
@@ -258,17 +271,67 @@ def check_rot_weight(rot_weight):
     return float(rot_weight)
 
 
-def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, select="consensus", rot_weight=1.0):
-    """Ranks the G candidate trajectories of every scene and selects one, in ONE launch (a3d_traj_rank, csrc/traj_rank.hip); nothing
-    is copied to the host.  trajectories: (B, G, L, Dp) fp32 poses [xyz | quaternion | opening], Dp = 7 or 8, scene-major as
-    compute_trajectory(num_samples=G) returns them, G <= 64; trajectory_mask: (B, L), non-zero = padded row (any pattern); goal:
-    (B, >= 7) pose rows, read in place where they are row slices of a wider tensor; bounds: (2, 3).
-    Terms per candidate over the valid rows: "consensus" (mean pose distance to all candidates of the scene: its argmin is the
-    medoid), "goal" (pose distance of the last valid row to the goal), "smooth" (mean squared second difference of the positions),
-    "length" (path length), "bounds" (share of rows outside the bounds); pose distance = position L2 + rot_weight (1 - <q, r>^2).
-    rot_weight = 1.0 is a choice, not a derived value: it prices a half turn (rho = 1) like one metre.  select: a preset name or a
-    dict of term weights (check_select).  Returns TrajectoryRanking(best (B,) int32, order (B, G) int32 ascending and stable,
-    scores (B, G), terms (B, G, 5), selected (B, L, Dp) = trajectories[b, best[b]]); a non-finite score counts as +inf."""
+def check_scene_select(select, have_goal=True, have_bounds=True, have_scene=True):
+    """check_select for rules that may also weigh the scene term: returns (the five weights in RANK_TERMS order, w_clearance).  The
+    preset "clear" puts weight 1 on "clearance"; a dict may map "clearance" to a finite, non-negative weight beside the five terms.
+    A rule whose only non-zero weight is the clearance is valid; a non-zero clearance weight needs a scene.  A rule that does not
+    name the term goes through check_select unchanged."""
+    if isinstance(select, str):
+        if select != CLEARANCE_PRESET:
+            return check_select(select, have_goal, have_bounds), 0.0
+        select = {CLEARANCE_TERM: 1.0}
+    if not isinstance(select, dict) or CLEARANCE_TERM not in select:
+        return check_select(select, have_goal, have_bounds), 0.0
+    v = select[CLEARANCE_TERM]
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError("select[%r] = %r: a weight is a finite, non-negative number" % (CLEARANCE_TERM, v))
+    wc = float(v)
+    rest = {k: x for k, x in select.items() if k != CLEARANCE_TERM}
+    if wc == 0.0:
+        return check_select(rest, have_goal, have_bounds), 0.0
+    if not have_scene:
+        raise ValueError("select weighs the clearance term, but no scene is given")
+    w = _term_weights(rest, have_goal, have_bounds, True)       # the other terms by the same checks; they may all be zero here
+    return w, wc
+
+
+def check_clearance_args(margin, skip):
+    """-> (margin, skip_head, skip_tail) of the clearance term, or ValueError"""
+    if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not math.isfinite(margin) or margin <= 0:
+        raise ValueError("margin must be a finite, positive number (metres), got %r" % (margin,))
+    if (not isinstance(skip, (tuple, list)) or len(skip) != 2
+            or any(isinstance(k, bool) or not isinstance(k, int) or k < 0 for k in skip)):
+        raise ValueError("skip must be two non-negative integers (rows skipped at the head, at the tail), got %r" % (skip,))
+    return float(margin), int(skip[0]), int(skip[1])
+
+
+def check_scene(scene, scene_mask, B):
+    """shape checks of a scene cloud (B, C, 3, H, W) or (B, N, 3) and its mask -> (n_cam, n_pix)"""
+    if not torch.is_tensor(scene) or scene.dim() not in (3, 5) or scene.shape[0] != B:
+        raise ValueError("scene must be (B, C, 3, H, W) or (B, N, 3) with B = %d, got %s" % (
+            B, tuple(scene.shape) if torch.is_tensor(scene) else type(scene).__name__))
+    if scene.dim() == 5:
+        if scene.shape[2] != 3 or min(scene.shape[1], scene.shape[3], scene.shape[4]) < 1:
+            raise ValueError("scene must be (B, C, 3, H, W) with at least one point, got %s" % (tuple(scene.shape),))
+        n_cam, n_pix, mshape = scene.shape[1], scene.shape[3] * scene.shape[4], (B, scene.shape[1], scene.shape[3], scene.shape[4])
+    else:
+        if scene.shape[2] != 3 or scene.shape[1] < 1:
+            raise ValueError("scene must be (B, N, 3) with at least one point, got %s" % (tuple(scene.shape),))
+        n_cam, n_pix, mshape = 1, scene.shape[1], (B, scene.shape[1])
+    if not scene.is_floating_point():
+        raise ValueError("scene must be a floating-point tensor, got %s" % scene.dtype)
+    if scene_mask is not None:
+        if not torch.is_tensor(scene_mask) or tuple(scene_mask.shape) != mshape:
+            raise ValueError("scene_mask must be %s (one entry per point of scene), got %s" % (
+                mshape, tuple(scene_mask.shape) if torch.is_tensor(scene_mask) else type(scene_mask).__name__))
+        if scene_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("scene_mask must be bool or uint8, got %s" % scene_mask.dtype)
+    if n_cam * n_pix > 0x7fffffff:
+        raise ValueError("scene has %d points per scene; the kernel addresses at most 2^31 - 1" % (n_cam * n_pix))
+    return n_cam, n_pix
+
+
+def _check_candidates(trajectories, trajectory_mask):
     if not torch.is_tensor(trajectories) or trajectories.dim() != 4:
         raise ValueError("trajectories must be a (B, G, L, Dp) tensor, got %s" % (
             tuple(trajectories.shape) if torch.is_tensor(trajectories) else type(trajectories).__name__,))
@@ -282,6 +345,65 @@ def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, sel
     if not torch.is_tensor(trajectory_mask) or tuple(trajectory_mask.shape) != (B, Ln):
         raise ValueError("trajectory_mask must be (B, L) = %s, got %s" % (
             (B, Ln), tuple(trajectory_mask.shape) if torch.is_tensor(trajectory_mask) else type(trajectory_mask).__name__))
+    return B, G, Ln, Dp
+
+
+def _mask_bytes(tm):
+    tm = tm.detach()
+    return O._c(tm).view(torch.uint8) if tm.dtype == torch.bool else O._c((tm != 0).view(torch.uint8) if tm.dtype != torch.uint8 else tm)
+
+
+def trajectory_clearance(trajectories, trajectory_mask, scene, scene_mask=None, margin=0.05, skip=(1, 1)):
+    """Distance of every waypoint of every candidate to the nearest observed scene point, and a clearance term per candidate, in TWO
+    launches (a3d_traj_clearance, csrc/traj_clearance.hip): brute force over the cloud, no (rows x points) matrix, no host copy.
+    trajectories: (B, G, L, Dp) fp32 poses in world coordinates as compute_trajectory returns them, Dp = 7 or 8 (only xyz is
+    read), G <= 64; trajectory_mask: (B, L), non-zero = padded row (any pattern).  scene: the observed cloud in world coordinates,
+    (B, C, 3, H, W) fp32 -- compute_trajectory's pcd_obs -- read in place when contiguous, or (B, N, 3) point rows, which are
+    transposed ONCE to (B, 1, 3, N) (one copy of the cloud).  scene_mask: (B, C, H, W) (or (B, N)) bool / uint8, non-zero = ignore
+    the point (RLBench's robot mask).  A point counts when it is not masked and its coordinates are finite.
+    Returns TrajectoryClearance(nearest (B, G, L), clearance (B, G)).  nearest: min over the counted points of |p - s|_2 (+inf
+    without a counted point and on padded rows, NaN where the row's xyz is not finite).  clearance: with j the rank of a valid row
+    among the n valid rows of its scene, the mean over the rows skip[0] <= j < n - skip[1] of max(0, margin - nearest) / margin, in
+    [0, 1]: 0 = every scored waypoint keeps at least `margin` metres clear, 1 = every one touches a point; 0 without a scored row,
+    NaN as soon as a scored row is NaN.  margin = 0.05 and skip = (1, 1) are choices, not derived values: 5 cm is about a finger
+    length of the Franka gripper, and row 0 (the in-painted current pose) and the last valid row (the goal) are where contact is
+    intended.  Bit-identical from run to run."""
+    B, G, Ln, Dp = _check_candidates(trajectories, trajectory_mask)
+    n_cam, n_pix = check_scene(scene, scene_mask, B)
+    mg, sh, st = check_clearance_args(margin, skip)
+    O.L.require_gpu(trajectories, trajectory_mask, scene, scene_mask)
+    P = O._c(trajectories.detach().float())
+    tm = _mask_bytes(trajectory_mask)
+    S = scene.detach().float()
+    S = O._c(S) if S.dim() == 5 else S.transpose(1, 2).contiguous()       # (B, N, 3) -> (B, 3, N) = (B, 1, 3, N): the one copy
+    sm = None if scene_mask is None else _mask_bytes(scene_mask)
+    dev = P.device
+    nearest = torch.empty((B, G, Ln), device=dev, dtype=torch.float32)
+    clearance = torch.empty((B, G), device=dev, dtype=torch.float32)
+    ws = torch.empty((O.L.load().a3d_traj_clearance_ws_floats(B, G, Ln, n_cam * n_pix, 0),), device=dev, dtype=torch.float32)
+    O.L.call("a3d_traj_clearance", P.data_ptr(), tm.data_ptr(), S.data_ptr(), None if sm is None else sm.data_ptr(), n_cam, n_pix, mg,
+             sh, st, nearest.data_ptr(), clearance.data_ptr(), ws.data_ptr(), 0, B, G, Ln, Dp, O.L.stream())
+    return TrajectoryClearance(nearest, clearance)
+
+
+def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, select="consensus", rot_weight=1.0, scene=None,
+                      scene_mask=None, margin=0.05, skip=(1, 1)):
+    """Ranks the G candidate trajectories of every scene and selects one, in ONE launch (a3d_traj_rank, csrc/traj_rank.hip); nothing
+    is copied to the host.  trajectories: (B, G, L, Dp) fp32 poses [xyz | quaternion | opening], Dp = 7 or 8, scene-major as
+    compute_trajectory(num_samples=G) returns them, G <= 64; trajectory_mask: (B, L), non-zero = padded row (any pattern); goal:
+    (B, >= 7) pose rows, read in place where they are row slices of a wider tensor; bounds: (2, 3).
+    Terms per candidate over the valid rows: "consensus" (mean pose distance to all candidates of the scene: its argmin is the
+    medoid), "goal" (pose distance of the last valid row to the goal), "smooth" (mean squared second difference of the positions),
+    "length" (path length), "bounds" (share of rows outside the bounds); pose distance = position L2 + rot_weight (1 - <q, r>^2).
+    rot_weight = 1.0 is a choice, not a derived value: it prices a half turn (rho = 1) like one metre.  select: a preset name or a
+    dict of term weights (check_select).  Returns TrajectoryRanking(best (B,) int32, order (B, G) int32 ascending and stable,
+    scores (B, G), terms (B, G, 5), selected (B, L, Dp) = trajectories[b, best[b]]); a non-finite score counts as +inf.
+    scene / scene_mask / margin / skip: the arguments of trajectory_clearance.  A rule that weighs "clearance" (a dict entry, or the
+    preset "clear") needs `scene`; the score is then the five-term sum plus w_clearance * clearance, added last, the call runs
+    trajectory_clearance's two launches before the ranking launch (a3d_traj_rank_extra, the same kernel) and returns
+    SceneTrajectoryRanking: the five fields above in order, then clearance (B, G) and nearest (B, G, L).  A rule that does not weigh
+    the term runs the one launch above and returns TrajectoryRanking, whatever `scene` is."""
+    B, G, Ln, Dp = _check_candidates(trajectories, trajectory_mask)
     if goal is not None and (not torch.is_tensor(goal) or goal.dim() != 2 or goal.shape[0] != B or goal.shape[1] < 7):
         raise ValueError("goal must be (B, >= 7) pose rows with B = %d, got %s" % (
             B, tuple(goal.shape) if torch.is_tensor(goal) else type(goal).__name__))
@@ -289,12 +411,14 @@ def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, sel
         bounds = torch.as_tensor(bounds, dtype=torch.float32, device=trajectories.device)
         if tuple(bounds.shape) != (2, 3):
             raise ValueError("bounds must be (2, 3), got %s" % (tuple(bounds.shape),))
-    w = check_select(select, goal is not None, bounds is not None)
+    w, wc = check_scene_select(select, goal is not None, bounds is not None, scene is not None)
     rw = check_rot_weight(rot_weight)
+    if wc != 0.0:
+        check_scene(scene, scene_mask, B)
+        check_clearance_args(margin, skip)
     O.L.require_gpu(trajectories, trajectory_mask, goal, bounds)
     P = O._c(trajectories.detach().float())
-    tm = trajectory_mask.detach()
-    tm = O._c(tm).view(torch.uint8) if tm.dtype == torch.bool else O._c((tm != 0).view(torch.uint8) if tm.dtype != torch.uint8 else tm)
+    tm = _mask_bytes(trajectory_mask)
     gl, ldg = (None, 0) if goal is None else _pose_rows(goal, "goal")
     dev = P.device
     best = torch.empty((B,), device=dev, dtype=torch.int32)
@@ -302,6 +426,13 @@ def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, sel
     scores = torch.empty((B, G), device=dev, dtype=torch.float32)
     terms = torch.empty((B, G, 5), device=dev, dtype=torch.float32)
     selected = torch.empty((B, Ln, Dp), device=dev, dtype=torch.float32)
+    if wc != 0.0:
+        cl = trajectory_clearance(P, tm, scene, scene_mask, margin, skip)
+        O.L.call("a3d_traj_rank_extra", P.data_ptr(), tm.data_ptr(), None if gl is None else gl.data_ptr(), ldg,
+                 None if bounds is None else O._c(bounds).data_ptr(), w[0], w[1], w[2], w[3], w[4], rw, best.data_ptr(),
+                 order.data_ptr(), scores.data_ptr(), terms.data_ptr(), selected.data_ptr(), B, G, Ln, Dp, cl.clearance.data_ptr(), wc,
+                 O.L.stream())
+        return SceneTrajectoryRanking(best, order, scores, terms, selected, cl.clearance, cl.nearest)
     O.L.call("a3d_traj_rank", P.data_ptr(), tm.data_ptr(), None if gl is None else gl.data_ptr(), ldg,
              None if bounds is None else O._c(bounds).data_ptr(), w[0], w[1], w[2], w[3], w[4], rw, best.data_ptr(), order.data_ptr(),
              scores.data_ptr(), terms.data_ptr(), selected.data_ptr(), B, G, Ln, Dp, O.L.stream())
@@ -1007,7 +1138,8 @@ class DiffusionPlanner(nn.Module):
     def compute_trajectory(self, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, *,
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
                            return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None,
-                           fused_conditioning=False, select=None, rot_weight=1.0):
+                           fused_conditioning=False, select=None, rot_weight=1.0, scene_mask=None, clear_margin=0.05,
+                           clear_skip=(1, 1)):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
@@ -1026,7 +1158,11 @@ class DiffusionPlanner(nn.Module):
         ranked on the device in one launch after signal_to_pose (with use_graph: after the replay) and the call returns the
         selected trajectory (B, L, 8), the single-trajectory shape; the goal and the workspace bounds of the ranking are this call's
         goal_gripper and gripper_loc_bounds, rot_weight its rotation weight.  self.last_ranking keeps best / order / scores / terms /
-        selected and all candidates (B, G, L, 8).  Trace entries stay (B, G, L, D).  None (default): today's path and result."""
+        selected and all candidates (B, G, L, 8).  Trace entries stay (B, G, L, D).  None (default): today's path and result.
+        A rule that weighs "clearance" (or the preset "clear") scores the candidates against THIS call's pcd_obs, the caller's
+        tensor in world coordinates, read in place (trajectory_clearance); scene_mask (B, C, H, W) drops points (the robot's own),
+        clear_margin / clear_skip are its margin and skip.  self.last_ranking then also carries clearance (B, G) and nearest
+        (B, G, L), before candidates."""
         head = self.prediction_head
         dev = pcd_obs.device
         B, Ln = trajectory_mask.shape
@@ -1039,9 +1175,13 @@ class DiffusionPlanner(nn.Module):
                 raise ValueError("select serves at most %d candidates per scene, num_samples is %d" % (RANK_MAX_CANDIDATES, G))
             if curr_gripper.shape[-1] not in (7, 8):
                 raise ValueError("select ranks pose rows of 7 or 8 channels, curr_gripper has %d" % curr_gripper.shape[-1])
-            check_select(select, goal_gripper is not None, True)
+            _, w_clear = check_scene_select(select, goal_gripper is not None, True, True)
             check_rot_weight(rot_weight)
+            if w_clear != 0.0:
+                check_scene(pcd_obs, scene_mask, B)
+                check_clearance_args(clear_margin, clear_skip)
             rank_mask, rank_goal = trajectory_mask, goal_gripper        # per scene: the fallback paths below expand their own copies
+            rank_scene = pcd_obs                                         # the caller's tensor, in world coordinates
         scheduled = num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0
         if scheduled:
             K = check_sampler_args(self.n_steps, num_inference_steps, scheduler, eta)
@@ -1193,8 +1333,9 @@ class DiffusionPlanner(nn.Module):
             final = final.reshape(B_scene, G, Ln, final.shape[-1])
             trace = [x.reshape(B_scene, G, Ln, x.shape[-1]) for x in trace]
         if select is not None:
-            rk = rank_trajectories(final, rank_mask, rank_goal, self.gripper_loc_bounds, select, rot_weight)
-            self.last_ranking = PlannerRanking(*rk, candidates=final)
+            rk = rank_trajectories(final, rank_mask, rank_goal, self.gripper_loc_bounds, select, rot_weight, scene=rank_scene,
+                                   scene_mask=scene_mask, margin=clear_margin, skip=clear_skip)
+            self.last_ranking = (ScenePlannerRanking if len(rk) == 7 else PlannerRanking)(*rk, candidates=final)
             final = rk.selected
         return (final, trace) if return_trace else final
 

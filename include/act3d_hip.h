@@ -432,6 +432,33 @@ int a3d_traj_condition(const float* curr, int ldc, const float* goal, int ldg, c
 int a3d_traj_rank(const float* poses, const unsigned char* tmask, const float* goal, int ldg, const float* bounds,
                   float w_consensus, float w_goal, float w_smooth, float w_length, float w_bounds, float rot_weight, int* best,
                   int* order, float* scores, float* terms, float* selected, int B, int G, int L, int Dp, void* stream);
+/* a3d_traj_rank with one more term: scores[b][g] = the five-term sum above, then + w_extra * extra[b][g], added last, when and
+ * only when w_extra != 0 (an unweighed extra is not read into the score, so its NaNs stay out).  extra: NULL or device [B][G], a
+ * term computed by another launch (a3d_traj_clearance); w_extra finite and >= 0, a non-zero one needs extra.  The same kernel:
+ * with extra = NULL and w_extra = 0 every output has the bits of a3d_traj_rank.  terms stays [B][G][5]. */
+int a3d_traj_rank_extra(const float* poses, const unsigned char* tmask, const float* goal, int ldg, const float* bounds,
+                        float w_consensus, float w_goal, float w_smooth, float w_length, float w_bounds, float rot_weight, int* best,
+                        int* order, float* scores, float* terms, float* selected, int B, int G, int L, int Dp, const float* extra,
+                        float w_extra, void* stream);
+/* Clearance of the sampled candidates from the observed scene cloud, by brute force, in two launches (csrc/traj_clearance.hip).
+ * None in the reference.  poses: [B][G][L][Dp], Dp = 7 or 8, world coordinates, only xyz is read; tmask: [B][L] bytes, non-zero =
+ * padded row (any pattern); scene: [B][n_cam][3][n_pix] fp32 world coordinates, channel-planar per camera (compute_trajectory's
+ * pcd_obs, read in place), N = n_cam n_pix points per scene; scene_mask: NULL or [B][n_cam][n_pix] bytes, non-zero = ignore the
+ * point.  A point counts when it is not masked and its three coordinates are finite.
+ *   nearest[b][g][i]  min over the counted points of |p - s|_2: d^2 = dx dx + dy dy + dz dz from the three differences (never
+ *                     |a|^2 + |b|^2 - 2ab), the minimum over d^2, one square root per row.  +inf without a counted point and for
+ *                     padded rows (not computed); NaN where the row's xyz is not finite.  May be NULL.
+ *   clearance[b][g]   mean over the scored rows of max(0, margin - nearest) / margin, in [0, 1]; j = rank of a valid row among the
+ *                     scene's n valid rows, scored: skip_head <= j < n - skip_tail; 0 without a scored row; NaN as soon as a
+ *                     scored row's nearest is NaN.
+ * ws: a3d_traj_clearance_ws_floats(B, G, L, N, n_chunks) floats owned by the caller (partial minima [n_chunks][B][G][L] and B L
+ * flags); n_chunks = how many pieces the points of a scene are cut into, 0 = chosen by the entry from the shapes alone.  The
+ * minimum is exact: nearest and clearance are bit-identical from run to run and for every n_chunks.  Stream-ordered, no host
+ * synchronisation, capturable.  margin finite and > 0; skips >= 0; G <= 64; B <= 65535. */
+size_t a3d_traj_clearance_ws_floats(int B, int G, int L, int n_points, int n_chunks);
+int a3d_traj_clearance(const float* poses, const unsigned char* tmask, const float* scene, const unsigned char* scene_mask, int n_cam,
+                       int n_pix, float margin, int skip_head, int skip_tail, float* nearest, float* clearance, float* ws,
+                       int n_chunks, int B, int G, int L, int Dp, void* stream);
 /* cols[b][9] of TrajectoryCriterion.compute_metrics (main_trajectory.py:303-343), see diffusion.hip; pred, gt: [B][L][D], D >= 7. */
 int a3d_traj_errors(const float* pred, const float* gt, float* cols, int B, int L, int D, void* stream);
 /* cols[b][6 + nlev] of LossAndMetrics.compute_metrics (main_keypose.py:431-482), see heads.hip; pos: [nlev + 1][B][3] with
