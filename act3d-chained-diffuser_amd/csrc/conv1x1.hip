@@ -35,8 +35,19 @@ __device__ __forceinline__ int c1_woff(int row, int seg) { return row * 32 + ((s
 // the convolution's bias (fp32, the first nbias channels) and the nearest-2x-upsampled coarser map top [images][H/2][W/2][N] bf16 to
 // the fp32 accumulators before the ONE rounding, y = x w^T + bias + up2(top): the lateral map is never written and re-read by a
 // top-down pass (a3d_upsample2_add_fwd: 1.2 GB of traffic for the 128 x 128 level of 256 images).
-struct C1Epilogue { const float* bias; int nbias; const unsigned short* top; int H, W; };
-template <int WN, int KS, bool EP = false>
+// RS (the bottleneck's conv3 with the block's final BatchNorm-apply + add + ReLU as its epilogue, a3d_conv1x1_bn_residual_fwd): bn3's
+// scale / shift are known BEFORE the GEMM (from the Gram matrix of its input, bn_gram.hip), so the epilogue forms
+//   y = bf16(max(acc osc[c] + osh[c] + r, lo)),  r = res[m][c] rsc[c] + rsh[c]  (rsc = 1, rsh = 0 without a folded downsample BatchNorm)
+// from the fp32 accumulators: the raw conv3 map is never written and re-read by a3d_bn_apply.  The lane's residual row segments (32
+// bytes each) are fetched ahead of the last K step's MFMAs as EP fetches `top`; the four per-channel constant rows live in LDS.
+// round_conv: the accumulator is first rounded to bf16, as the raw conv3 map was when it was written, and the arithmetic of
+// bn_apply_kernel follows on that value -- with scale / shift from the statistics of the rounded outputs (the RS == 2 instances: the
+// plain kernel with its statistics epilogue and NO store of y) the result is a3d_conv1x1_bn_fwd + a3d_bn_apply's, bit for bit.
+struct C1Epilogue {
+  const float* bias; int nbias; const unsigned short* top; int H, W;
+  const float *osc, *osh; const unsigned short* res; const float *rsc, *rsh; float lo; int round_conv;
+};
+template <int WN, int KS, bool EP = false, int RS = 0>
 __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ w,
                                                              const float* __restrict__ in_scale, const float* __restrict__ in_shift,
                                                              int in_relu, unsigned short* __restrict__ y, float* __restrict__ partial,
@@ -48,6 +59,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const unsigned s
   unsigned short* Ws = smem_c1;                                   // [KS][BN * 32]
   unsigned short* Xs = Ws + KS * BN * 32;                         // [2][BM * 32]
   float* scS = reinterpret_cast<float*>(Xs + 2 * BM * 32);        // [K] scale | [K] shift
+  float* cS = scS + 2 * K;                                        // RS: [BN] osc | osh | rsc | rsh
   __shared__ float redS[4][64], redQ[4][64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int li = lane & 15, g = lane >> 4;
@@ -61,6 +73,13 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const unsigned s
   }
   if (in_scale)
     for (int i = t; i < K; i += 256) { scS[i] = in_scale[i]; scS[K + i] = in_shift[i]; }
+  if (RS == 1)
+    for (int i = t; i < BN; i += 256) {
+      cS[i] = ep.osc[n0 + i];
+      cS[BN + i] = ep.osh[n0 + i];
+      cS[2 * BN + i] = ep.rsc ? ep.rsc[n0 + i] : 1.f;               // r * 1 + 0 is r exactly: one code path
+      cS[3 * BN + i] = ep.rsc ? ep.rsh[n0 + i] : 0.f;
+    }
   float ssum[4][4], ssq[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -135,6 +154,16 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const unsigned s
         for (int tn = 0; tn < 4; ++tn)
           wb[tn] = *reinterpret_cast<const s16x8*>(&Ws[ks * BN * 32 + c1_woff(wn * 64 + (li >> 2) * 16 + tn * 4 + (li & 3), g)]);
         uint4 tv[4][2];                                           // EP: the top map's 16 channels under each of the lane's 4 rows
+        if (RS == 1 && ks == KS - 1) {                            // RS: the residual's 16 channels under each of the lane's 4 rows
+          const long long m0 = (blockIdx.x + (s / KS) * gridDim.x) * BM;
+#pragma unroll
+          for (int tm = 0; tm < 4; ++tm) {
+            const long long m = m0 + wm * 64 + tm * 16 + li;
+            const uint4* src = reinterpret_cast<const uint4*>(ep.res + (size_t)(m < M ? m : M - 1) * N + n0 + wn * 64 + g * 16);
+            tv[tm][0] = src[0];
+            tv[tm][1] = src[1];
+          }
+        }
         if (EP && ks == KS - 1 && ep.top) {                       // issued ahead of the MFMAs whose epilogue consumes them
           const long long m0 = (blockIdx.x + (s / KS) * gridDim.x) * BM;
 #pragma unroll
@@ -153,7 +182,46 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const unsigned s
         for (int tn = 0; tn < 4; ++tn)
 #pragma unroll
           for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = mfma_bf16_16x16x32(wb[tn], xa[tm], acc[tn][tm]);
-        if (ks == KS - 1) {
+        if (RS == 1 && ks == KS - 1) {
+          // tile done, RS: channel group tn outermost, so that only ITS constants (4 x 4 floats from LDS) are live next to the
+          // accumulators -- with the rows outermost the compiler kept all 64 in registers and the <4, 4> instance spilled
+          const long long m0 = (blockIdx.x + (s / KS) * gridDim.x) * BM;
+          unsigned int pk[4][8];
+#pragma unroll
+          for (int tn = 0; tn < 4; ++tn) {
+            const int cb = wn * 64 + g * 16 + tn * 4;              // channels 4 tn .. + 3 of the lane's 16
+            const float4 c_osc = *reinterpret_cast<const float4*>(&cS[cb]), c_osh = *reinterpret_cast<const float4*>(&cS[BN + cb]);
+            const float4 c_rsc = *reinterpret_cast<const float4*>(&cS[2 * BN + cb]), c_rsh = *reinterpret_cast<const float4*>(&cS[3 * BN + cb]);
+#pragma unroll
+            for (int tm = 0; tm < 4; ++tm) {
+#pragma unroll
+              for (int r2 = 0; r2 < 2; ++r2) {                     // word 2 tn + r2 of the lane's 16 channels = channels 4 tn + 2 r2, + 1
+                const uint4 q = tv[tm][tn >> 1];
+                const unsigned int rw = (tn & 1) ? (r2 ? q.w : q.z) : (r2 ? q.y : q.x);
+                const float r0 = fmaf(__uint_as_float(rw << 16), r2 ? c_rsc.z : c_rsc.x, r2 ? c_rsh.z : c_rsh.x);
+                const float r1 = fmaf(__uint_as_float(rw & 0xFFFF0000u), r2 ? c_rsc.w : c_rsc.y, r2 ? c_rsh.w : c_rsh.y);
+                float v0 = acc[tn][tm][2 * r2], v1 = acc[tn][tm][2 * r2 + 1];
+                const unsigned int vr = pk_bf16(v0, v1);
+                v0 = ep.round_conv ? __uint_as_float(vr << 16) : v0;
+                v1 = ep.round_conv ? __uint_as_float(vr & 0xFFFF0000u) : v1;
+                const float a0 = fmaxf(fmaf(v0, r2 ? c_osc.z : c_osc.x, r2 ? c_osh.z : c_osh.x) + r0, ep.lo);
+                const float a1 = fmaxf(fmaf(v1, r2 ? c_osc.w : c_osc.y, r2 ? c_osh.w : c_osh.y) + r1, ep.lo);
+                pk[tm][2 * tn + r2] = pk_bf16(a0, a1);
+              }
+              acc[tn][tm] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+          }
+#pragma unroll
+          for (int tm = 0; tm < 4; ++tm) {
+            const long long m = m0 + wm * 64 + tm * 16 + li;
+            if (m < M) {
+              uint4* dst = reinterpret_cast<uint4*>(y + (size_t)m * N + n0 + wn * 64 + g * 16);
+              dst[0] = make_uint4(pk[tm][0], pk[tm][1], pk[tm][2], pk[tm][3]);
+              dst[1] = make_uint4(pk[tm][4], pk[tm][5], pk[tm][6], pk[tm][7]);
+            }
+          }
+        }
+        if (RS != 1 && ks == KS - 1) {
           // tile done: round once; the weight rows were fed to the MFMA permuted (tile tn row i <-> channel (i >> 2) * 16 + tn * 4 +
           // (i & 3) of the wave's 64), so a lane holds 16 CONSECUTIVE channels of its row: 32-byte stores, and the four lane groups
           // of a row write one full 128-byte line (8-byte stores of 4 channels reached 3.25 TB/s on the 64 -> 256 layers against
@@ -193,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const unsigned s
               }
               acc[tn][tm] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            if (ok) {
+            if (ok && RS != 2) {                                 // RS == 2: statistics only
               uint4* dst = reinterpret_cast<uint4*>(y + (size_t)m * N + n0 + wn * 64 + g * 16);
               dst[0] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
               dst[1] = make_uint4(pk[4], pk[5], pk[6], pk[7]);
@@ -203,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const unsigned s
       }
     }
   }
-  if (EP || !partial) return;
+  if (EP || RS == 1 || !partial) return;
 #pragma unroll
   for (int tn = 0; tn < 4; ++tn)
 #pragma unroll
@@ -231,9 +299,9 @@ using namespace a3d;
 
 static int c1_wn(int N) { return N >= 256 ? 4 : (N >= 128 ? 2 : 1); }
 // dynamic LDS of the streaming kernel: W block + two X buffers + scale / shift
-static size_t c1_stream_lds(int K, int N) {
+static size_t c1_stream_lds(int K, int N, bool rs = false) {
   const int wn = c1_wn(N), bn = 64 * wn, bm = 64 * (4 / wn);
-  return (size_t)(K / 32) * bn * 64 + (size_t)2 * bm * 64 + (size_t)2 * K * sizeof(float);
+  return (size_t)(K / 32) * bn * 64 + (size_t)2 * bm * 64 + (size_t)2 * K * sizeof(float) + (rs ? (size_t)4 * bn * sizeof(float) : 0);
 }
 // the shapes the resident-weight kernel serves: K in {64, 128, 256}, its LDS block within 96 KB (two workgroups per CU up to 78 KB)
 static bool c1_streams(int K, int N) {
@@ -274,7 +342,8 @@ extern "C" int a3d_conv1x1_nslab(size_t M, int K, int N) {
 
 extern "C" int a3d_conv1x1_bn_fwd(const void* x, const void* w, const float* in_scale, const float* in_shift, int in_relu,
                                   void* y, float* partial, size_t M, int K, int N, void* stream) {
-  if (!x || !w || !y || M == 0 || K <= 0 || N <= 0 || !(c1_streams(K, N) || c1_deep(K, N)) || (in_scale && !in_shift) ||
+  const bool stats_only = !y && partial && ((K == 64 && N == 256) || (K == 128 && N == 512));      // (a3d_conv1x1_bn_residual_serves)
+  if (!x || !w || (!y && !stats_only) || M == 0 || K <= 0 || N <= 0 || !(c1_streams(K, N) || c1_deep(K, N)) || (in_scale && !in_shift) ||
       ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15) != 0)) {
     set_error("a3d_conv1x1_bn_fwd: bad argument (M=%zu K=%d N=%d; served shapes: K in {64, 128, 256}, N in {64, 128, 256 j}, weight block "
               "+ buffers within 96 KB of LDS (the resident-weight kernel), or K = 64 j in 128 .. 2048 and N = 128 j up to 2048 (the deep-layer "
@@ -293,10 +362,18 @@ extern "C" int a3d_conv1x1_bn_fwd(const void* x, const void* w, const float* in_
   do {                                                                                                                           \
     static bool once = false;                                                                                                    \
     if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WNV, KSV>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; } \
-    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV>), grid, dim3(256), lds, s, xs, ws, in_scale, in_shift, in_relu, ys, partial, (long long)M, N, C1Epilogue{nullptr, 0, nullptr, 0, 0}); \
+    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV>), grid, dim3(256), lds, s, xs, ws, in_scale, in_shift, in_relu, ys, partial, (long long)M, N, C1Epilogue{nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0}); \
+  } while (0)
+#define A3D_C1N(WNV, KSV)                                                                                                         \
+  do {                                                                                                                           \
+    static bool once = false;                                                                                                    \
+    if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WNV, KSV, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; } \
+    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV, false, 2>), grid, dim3(256), lds, s, xs, ws, in_scale, in_shift, in_relu, ys, partial, (long long)M, N, C1Epilogue{nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0}); \
   } while (0)
   const int wn = c1_wn(N), ks = K / 32;
-  if (wn == 4 && ks == 2) A3D_C1S(4, 2);
+  if (stats_only && ks == 2) A3D_C1N(4, 2);
+  else if (stats_only) A3D_C1N(4, 4);
+  else if (wn == 4 && ks == 2) A3D_C1S(4, 2);
   else if (wn == 4 && ks == 4) A3D_C1S(4, 4);
   else if (wn == 2 && ks == 2) A3D_C1S(2, 2);
   else if (wn == 2 && ks == 4) A3D_C1S(2, 4);
@@ -306,6 +383,7 @@ extern "C" int a3d_conv1x1_bn_fwd(const void* x, const void* w, const float* in_
   else if (wn == 1 && ks == 8) A3D_C1S(1, 8);
   else { set_error("a3d_conv1x1_bn_fwd: no streaming instance for K=%d N=%d", K, N); return A3D_ERR_ARG; }
 #undef A3D_C1S
+#undef A3D_C1N
   return check_launch("a3d_conv1x1_bn_fwd");
 }
 
@@ -325,7 +403,7 @@ extern "C" int a3d_conv1x1_topdown_fwd(const void* x, const void* w, const float
   const int slabs = c1_slabs(M, K, N);
   const size_t lds = c1_stream_lds(K, N);
   const dim3 grid(slabs, 1);
-  const C1Epilogue ep{bias, bias ? nbias : 0, (const unsigned short*)top, H, W};
+  const C1Epilogue ep{bias, bias ? nbias : 0, (const unsigned short*)top, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0};
 #define A3D_C1E(WNV, KSV)                                                                                                         \
   do {                                                                                                                           \
     static bool once = false;                                                                                                    \
@@ -343,4 +421,35 @@ extern "C" int a3d_conv1x1_topdown_fwd(const void* x, const void* w, const float
   else { set_error("a3d_conv1x1_topdown_fwd: no streaming instance for K=%d N=%d", K, N); return A3D_ERR_ARG; }
 #undef A3D_C1E
   return check_launch("a3d_conv1x1_topdown_fwd");
+}
+
+// the bottleneck conv3 shapes of the HBM-bound layers 1 and 2 (the <4, 2> and <4, 4> instances); layers 3 - 4 go through the deep GEMM
+extern "C" int a3d_conv1x1_bn_residual_serves(int K, int N) { return ((K == 64 && N == 256) || (K == 128 && N == 512)) ? 1 : 0; }
+
+extern "C" int a3d_conv1x1_bn_residual_fwd(const void* x, const void* w, const float* in_scale, const float* in_shift, int in_relu,
+                                           const float* out_scale, const float* out_shift, const void* res, const float* res_scale,
+                                           const float* res_shift, int relu, int round_conv, void* y, size_t M, int K, int N, void* stream) {
+  if (!x || !w || !y || !res || !out_scale || !out_shift || M == 0 || !a3d_conv1x1_bn_residual_serves(K, N) || (in_scale && !in_shift) ||
+      ((res_scale != nullptr) != (res_shift != nullptr)) || ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)res) & 15) != 0)) {
+    set_error("a3d_conv1x1_bn_residual_fwd: bad argument (M=%zu K=%d N=%d; served: 64 -> 256 and 128 -> 512 -- a3d_conv1x1_bn_residual_serves; "
+              "out_scale / out_shift and a residual are required, in_shift with in_scale, res_shift with res_scale, 16-byte aligned operands)",
+              M, K, N);
+    return A3D_ERR_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int slabs = c1_slabs(M, K, N);
+  const size_t lds = c1_stream_lds(K, N, true);
+  const dim3 grid(slabs, N / 256);
+  const C1Epilogue ep{nullptr, 0, nullptr, 0, 0, out_scale, out_shift, (const unsigned short*)res, res_scale, res_shift, relu ? 0.f : -INFINITY, round_conv ? 1 : 0};
+#define A3D_C1R(WNV, KSV)                                                                                                         \
+  do {                                                                                                                           \
+    static bool once = false;                                                                                                    \
+    if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WNV, KSV, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; } \
+    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV, false, 1>), grid, dim3(256), lds, s, (const unsigned short*)x, (const unsigned short*)w, \
+                       in_scale, in_shift, in_relu, (unsigned short*)y, (float*)nullptr, (long long)M, N, ep);                    \
+  } while (0)
+  if (K == 64) A3D_C1R(4, 2);
+  else A3D_C1R(4, 4);
+#undef A3D_C1R
+  return check_launch("a3d_conv1x1_bn_residual_fwd");
 }

@@ -157,6 +157,11 @@ SIGNATURES = {
     "a3d_conv1x1_bn_fwd": (_i, [_p, _p, _p, _p, _i, _p, _p, _z, _i, _i, _p]),
     "a3d_conv1x1_topdown_serves": (_i, [_i, _i]),
     "a3d_conv1x1_topdown_fwd": (_i, [_p, _p, _p, _i, _p, _p, _z, _i, _i, _i, _i, _p]),
+    "a3d_conv1x1_bn_residual_serves": (_i, [_i, _i]),
+    "a3d_conv1x1_bn_residual_fwd": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _z, _i, _i, _p]),
+    "a3d_bn_gram_nslab": (_i, [_z, _i]),
+    "a3d_bn_gram": (_i, [_p, _p, _p, _i, _p, _p, _z, _i, _i, _p]),
+    "a3d_bn_gram_stats": (_i, [_p, _p, _i, _p, _i, _i, _p, _p, _p]),
     "a3d_conv3x3_serves": (_i, [_i, _i, _i, _i]),
     "a3d_conv1x1_deep_mode": (_i, [_i]),
     "a3d_stem_conv_nslab": (_i, [_z, _i, _i]),

@@ -554,6 +554,67 @@ def conv1x1_bn(x, conv, in_scale=None, in_relu=False, want_stats=True):
     return y, partial
 
 
+def conv1x1_gram_stats(x, conv, in_scale=None, in_relu=False):
+    """(1, 2, Cout) fp32 (sum, sum of squares) over rows of the OUTPUT of the 1x1 convolution `conv` on the bf16 channels_last x
+    (with the producer's BatchNorm-apply `in_scale` folded in as conv1x1_bn folds it), computed from the K x K Gram matrix of its
+    INPUT (csrc/bn_gram.hip): the record bn_scale_shift(partial=...) finalizes -- the statistics exist before the convolution runs."""
+    N, K, H, W = x.shape
+    Cout = conv.weight.shape[0]
+    assert x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last) and conv.weight.dtype == torch.bfloat16
+    M = N * H * W
+    w2 = conv.weight.reshape(Cout, K)
+    assert w2.is_contiguous()
+    dev, st = x.device, O.L.stream()
+    nslab = O.L.load().a3d_bn_gram_nslab(M, K)
+    part = torch.empty((nslab * (K * K + K),), device=dev, dtype=torch.float32)
+    gpart, spart = part[:nslab * K * K], part[nslab * K * K:]
+    work = torch.empty((K * K + K,), device=dev, dtype=torch.float64)
+    stats = torch.empty((1, 2, Cout), device=dev, dtype=torch.float32)
+    O.L.call("a3d_bn_gram", x.data_ptr(), None if in_scale is None else in_scale[0].data_ptr(),
+             None if in_scale is None else in_scale[1].data_ptr(), 1 if in_relu else 0, gpart.data_ptr(), spart.data_ptr(), M, K, nslab, st)
+    O.L.call("a3d_bn_gram_stats", gpart.data_ptr(), spart.data_ptr(), nslab, w2.data_ptr(), K, Cout, work.data_ptr(), stats.data_ptr(), st)
+    return stats
+
+
+def conv1x1_stats_only(x, conv, in_scale=None, in_relu=False):
+    """the `partial` statistics conv1x1_bn would return for the bottleneck's conv3, WITHOUT its output: the same kernel, the same sums
+    of the bf16-rounded outputs, nothing stored (a3d_conv1x1_bn_fwd with y = NULL)."""
+    N, K, H, W = x.shape
+    Cout = conv.weight.shape[0]
+    assert x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last) and conv.weight.dtype == torch.bfloat16
+    M = N * H * W
+    w2 = conv.weight.reshape(Cout, K)
+    assert w2.is_contiguous()
+    partial = torch.empty((O.L.load().a3d_conv1x1_nslab(M, K, Cout), 2, Cout), device=x.device, dtype=torch.float32)
+    O.L.call("a3d_conv1x1_bn_fwd", x.data_ptr(), w2.data_ptr(), None if in_scale is None else in_scale[0].data_ptr(),
+             None if in_scale is None else in_scale[1].data_ptr(), 1 if in_relu else 0, None, partial.data_ptr(), M, K, Cout, O.L.stream())
+    return partial
+
+
+def conv1x1_bn_residual(x, conv, out_scale, residual, in_scale=None, in_relu=False, residual_scale=None, relu=True, out=None,
+                        round_conv=False):
+    """relu?(bn(conv(f(x))) + r) in ONE launch (a3d_conv1x1_bn_residual_fwd): the 1x1 convolution of conv1x1_bn with the BatchNorm-apply
+    of its OWN output (`out_scale` = bn_scale_shift of conv1x1_gram_stats), the residual add (`residual_scale`: the folded BatchNorm of
+    the downsample branch) and the ReLU as its epilogue, one rounding from the fp32 accumulator; the raw convolution output is never
+    written.  round_conv: the accumulator is rounded to bf16 first -- with `out_scale` from conv1x1_stats_only the result is
+    conv1x1_bn + bn_act's, bit for bit.  out: a preallocated tensor for the result."""
+    N, K, H, W = x.shape
+    Cout = conv.weight.shape[0]
+    assert x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
+    assert residual.shape == (N, Cout, H, W) and residual.dtype == torch.bfloat16 and residual.is_contiguous(memory_format=torch.channels_last)
+    w2 = conv.weight.reshape(Cout, K)
+    assert w2.is_contiguous()
+    if out is not None:
+        assert out.shape == residual.shape and out.dtype == torch.bfloat16 and out.is_contiguous(memory_format=torch.channels_last)
+    y = out if out is not None else torch.empty_like(residual)
+    O.L.call("a3d_conv1x1_bn_residual_fwd", x.data_ptr(), w2.data_ptr(), None if in_scale is None else in_scale[0].data_ptr(),
+             None if in_scale is None else in_scale[1].data_ptr(), 1 if in_relu else 0, out_scale[0].data_ptr(), out_scale[1].data_ptr(),
+             residual.data_ptr(), None if residual_scale is None else residual_scale[0].data_ptr(),
+             None if residual_scale is None else residual_scale[1].data_ptr(), 1 if relu else 0, 1 if round_conv else 0, y.data_ptr(),
+             N * H * W, K, Cout, O.L.stream())
+    return y
+
+
 def conv3x3_serves(x, conv):
     """the 3x3 convolution `conv` on the bf16 channels_last map x is one a3d_conv3x3_bn_fwd serves (stride 1, padding 1, no bias,
     32 -> 32 / 32 -> 64 / 64 -> 64 channels, H % 8 == 0, W % 32 == 0)"""
@@ -696,11 +757,23 @@ def fused_frozen_backbone_forward(bb, x, stem=None, out=None):
             return conv1x1_bn(t, m, **kw)
         return conv(m, t), None
 
+    def res_ok(m, t):
+        """conv3 m on the bf16 channels_last t goes through a3d_conv1x1_bn_residual_fwd: bn3 + add + ReLU in its epilogue"""
+        return bool(FUSED_CONV3_RESIDUAL and fuse and m.kernel_size == (1, 1) and m.stride == (1, 1) and m.bias is None and
+                    m.weight.dtype == torch.bfloat16 and t.dtype == torch.bfloat16 and t.is_contiguous(memory_format=torch.channels_last) and
+                    O.L.load().a3d_conv1x1_bn_residual_serves(t.shape[1], m.weight.shape[0]))
+
     for bi, blk in enumerate(blocks):
         c1, p1 = conv1(blk.conv1, x, want_stats=blk.bn1.training)
         c2, p2 = conv3(blk.conv2, c1, blk.bn1, p1, blk.bn2.training)
         no_pool = isinstance(blk.avgpool, nn.Identity) or (isinstance(blk.avgpool, nn.AvgPool2d) and blk.avgpool.kernel_size in (1, (1, 1)))
-        if no_pool and fused_ok(blk.conv3, c2):
+        nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
+        # (the pooled map a layer's last block also emits still comes from a3d_bn_apply_pool2: those blocks keep the raw conv3 map)
+        pooled_next = lambda t: nxt is not None and nxt.downsample is not None and _pool2_ok(nxt.downsample[0], t)   # t: conv3's input
+        o3 = p3 = a3 = a3_scale = None                   # a3 (+ a3_scale): conv3's input (+ its pending BatchNorm-apply) on the fused-residual route
+        if no_pool and not pooled_next(c2) and res_ok(blk.conv3, c2):
+            a3, a3_scale = c2, bn_scale_shift(c2, blk.bn2, p2)
+        elif no_pool and fused_ok(blk.conv3, c2):
             # BatchNorm-apply + ReLU of bn2 ride on conv3's operand load: c2 is never rewritten
             o3, p3 = conv1x1_bn(c2, blk.conv3, in_scale=bn_scale_shift(c2, blk.bn2, p2), in_relu=True, want_stats=blk.bn3.training)
         else:
@@ -708,7 +781,10 @@ def fused_frozen_backbone_forward(bb, x, stem=None, out=None):
                 out = bn_act(c2, blk.bn2, pool=True, keep_full=False, partial=p2)[1]
             else:
                 out = blk.avgpool(bn_act(c2, blk.bn2, partial=p2))
-            o3, p3 = conv1(blk.conv3, out, want_stats=blk.bn3.training)
+            if not pooled_next(out) and res_ok(blk.conv3, out):
+                a3 = out                                 # already normalised and pooled: no prologue
+            else:
+                o3, p3 = conv1(blk.conv3, out, want_stats=blk.bn3.training)
         if blk.downsample is not None:
             dpool = blk.downsample[0]
             if x_pooled is not None:
@@ -721,8 +797,7 @@ def fused_frozen_backbone_forward(bb, x, stem=None, out=None):
                 xin = dpool(x)
             cd, pd = conv1(blk.downsample[1], xin, want_stats=blk.downsample[2].training)
             bns.append(blk.downsample[2])
-        nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
-        want_pooled = nxt is not None and nxt.downsample is not None and _pool2_ok(nxt.downsample[0], o3)
+        want_pooled = a3 is None and pooled_next(o3)
         idn_scale = None
         if blk.downsample is None:
             idn = x
@@ -732,7 +807,18 @@ def fused_frozen_backbone_forward(bb, x, stem=None, out=None):
         else:
             idn = bn_act(cd, blk.downsample[2], relu=False, partial=pd)
         o_x = o_("res%d" % (len(outs) + 1)) if id(blk) in last_of_layer else None      # a layer's last block writes the returned map
-        if want_pooled:
+        if a3 is not None:
+            # bn3's statistics first (none in eval mode) -- the sums of the bf16-rounded conv3 outputs from a pass of the GEMM that stores
+            # nothing, or ("gram") of the unrounded product from the Gram matrix of conv3's input --, then conv3 + bn3 + add + ReLU in
+            # one launch: the raw conv3 map is never written
+            gram = FUSED_CONV3_RESIDUAL == "gram"
+            st3 = None
+            if blk.bn3.training:
+                st3 = (conv1x1_gram_stats if gram else conv1x1_stats_only)(a3, blk.conv3, in_scale=a3_scale, in_relu=a3_scale is not None)
+            sc3 = bn_scale_shift(idn, blk.bn3, partial=st3)        # (idn has conv3's output shape: rows and channels)
+            x, x_pooled = conv1x1_bn_residual(a3, blk.conv3, sc3, idn, in_scale=a3_scale, in_relu=a3_scale is not None,
+                                              residual_scale=idn_scale, relu=True, out=o_x, round_conv=not gram), None
+        elif want_pooled:
             x, x_pooled = bn_act(o3, blk.bn3, relu=True, residual=idn, pool=True, partial=p3, out=o_x)
         else:
             x, x_pooled = bn_act(o3, blk.bn3, relu=True, residual=idn, partial=p3, residual_scale=idn_scale, out=o_x), None
@@ -748,6 +834,16 @@ FUSED_BN = os.environ.get("A3D_FUSED_BN", "1") == "1"
 # BatchNorm of the bottleneck's downsample branch applied inside the block's final BatchNorm-apply + add + ReLU kernel (a second
 # scale / shift pair on the residual operand) instead of its own pass.  A3D_FOLD_DS_BN=0: the branch's map is materialised (A/B).
 FOLD_DOWNSAMPLE_BN = os.environ.get("A3D_FOLD_DS_BN", "1") not in ("0", "", "off")
+# conv3 of the layer-1 / layer-2 bottlenecks with bn3 + residual add + ReLU as its epilogue (a3d_conv1x1_bn_residual_fwd): bn3's batch
+# statistics exist before the GEMM that applies them runs, so the raw conv3 map is never written and re-read by the final
+# BatchNorm-apply.  True (default): the statistics of the bf16-ROUNDED conv3 outputs from a pass of the GEMM that stores nothing, and
+# an epilogue that rounds the accumulator first -- the block output is the unfused path's, bit for bit.  "gram"
+# (A3D_FUSED_CONV3_RES=gram): the statistics of the unrounded product from the K x K Gram matrix of conv3's INPUT (a3d_bn_gram) and
+# one rounding from the accumulator: cheaper (no second GEMM), and every block output moves by up to a bf16 ulp -- which the deep
+# layers of this network amplify to tens of percent of res5's rms, like any other perturbation of that size.
+# A3D_FUSED_CONV3_RES=0: conv3 + a3d_bn_apply as before (A/B).
+_c3r = os.environ.get("A3D_FUSED_CONV3_RES", "1")
+FUSED_CONV3_RESIDUAL = False if _c3r in ("0", "", "off") else ("gram" if _c3r == "gram" else True)
 # The backbone's 1x1 convolutions of the HBM-bound layers (1 and 2: K <= 256, the shapes a3d_conv1x1_streams accepts) through
 # a3d_conv1x1_bn_fwd, with BatchNorm-apply of the producer and the statistics of the consumer folded into the GEMM; the deep,
 # compute-bound layers stay on MIOpen (profiles/r04_conv1x1_layers.json).  A3D_FUSED_CONV1X1=0: MIOpen everywhere (A/B).

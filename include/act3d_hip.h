@@ -649,6 +649,33 @@ int a3d_conv1x1_bn_fwd(const void* x, const void* w, const float* in_scale, cons
 int a3d_conv1x1_topdown_serves(int K, int N);
 int a3d_conv1x1_topdown_fwd(const void* x, const void* w, const float* bias, int nbias, const void* top, void* y, size_t images,
                             int H, int W, int K, int N, void* stream);
+/* The bottleneck's conv3 with the block's final BatchNorm-apply + residual add + ReLU as its epilogue (CLIP ModifiedResNet Bottleneck.forward,
+ * model/utils/clip.py:28-43: out = relu(bn3(conv3(out)) + identity)):
+ *   y[m][c] = bf16( max( (f(x) w^T)[m][c] * out_scale[c] + out_shift[c] + r[m][c], relu ? 0 : -inf ) ),  ONE rounding, from the fp32 accumulator
+ *   r = res[m][c], or res[m][c] * res_scale[c] + res_shift[c] (the folded BatchNorm of the downsample branch; both NULL: plain)
+ * x, w, in_scale / in_shift / in_relu as a3d_conv1x1_bn_fwd; res, y [M][N] bf16; out_scale / out_shift = bn3's, which must exist before the
+ * GEMM runs: a3d_bn_gram + a3d_bn_gram_stats + a3d_bn_finalize give them from conv3's INPUT.  No statistics epilogue.
+ * round_conv != 0: the accumulator is rounded to bf16 first, as a3d_conv1x1_bn_fwd writes it, and a3d_bn_apply's arithmetic follows: with
+ * out_scale / out_shift from the statistics-only call of a3d_conv1x1_bn_fwd (y NULL, partial given: the same sums, nothing stored; these
+ * two shapes only) the result is a3d_conv1x1_bn_fwd + a3d_bn_finalize + a3d_bn_apply's, bit for bit.  Served
+ * (a3d_conv1x1_bn_residual_serves == 1): K -> N in {64 -> 256, 128 -> 512}, the conv3 shapes of layers 1 and 2; 16-byte aligned operands. */
+int a3d_conv1x1_bn_residual_serves(int K, int N);
+int a3d_conv1x1_bn_residual_fwd(const void* x, const void* w, const float* in_scale, const float* in_shift, int in_relu,
+                                const float* out_scale, const float* out_shift, const void* res, const float* res_scale,
+                                const float* res_shift, int relu, int round_conv, void* y, size_t M, int K, int N, void* stream);
+/* Batch statistics of a 1x1 convolution's output from its input (csrc/bn_gram.hip): with a = the bf16 A operand a3d_conv1x1_bn_fwd stages
+ * from x [M][K] (in_scale / in_shift / in_relu as there) and o = a w^T,  sum_m o[m][c] = w_c . sum_m a[m][:]  and
+ * sum_m o[m][c]^2 = w_c^T (a^T a) w_c.
+ * a3d_bn_gram: gpart [nslab][K][K] fp32 partial Gram matrices a^T a (bf16 MFMA, fp32 accumulation) and spart [nslab][K] fp32 column sums, one
+ * per persistent workgroup; rows are dealt in chunks of 8192 / K, chunk j to slab j % nslab; fixed assignment, no atomics: two launches
+ * give the same bits.  K in {64, 128}; nslab = a3d_bn_gram_nslab(M, K) (0: not served); operands 16-byte aligned.
+ * a3d_bn_gram_stats: the slabs reduced in a fixed order in double (work: K K + K doubles of scratch), then per output channel of
+ * w [N][K] bf16 both forms in double -> stats [1][2][N] fp32 (sum, sum of squares): the record a3d_bn_finalize reduces with nslab = 1. */
+int a3d_bn_gram_nslab(size_t M, int K);
+int a3d_bn_gram(const void* x, const float* in_scale, const float* in_shift, int in_relu, float* gpart, float* spart, size_t M, int K,
+                int nslab, void* stream);
+int a3d_bn_gram_stats(const float* gpart, const float* spart, int nslab, const void* w, int K, int N, double* work, float* stats,
+                      void* stream);
 /* Whether the deep-layer GEMM of a3d_conv1x1_bn_fwd (K = 64 j in 128 .. 2048, N = 128 j up to 2048: the 1x1 convolutions of CLIP
  * ModifiedResNet layers 2 - 4, model/utils/clip.py:28-43) takes its shapes: 1 yes (default; A3D_CONV1X1_DEEP), 0 they stay with the
  * library.  Sets the mode and returns the previous one; mode < 0 only queries.  Affects a3d_conv1x1_streams / _nslab / _bn_fwd alike. */
