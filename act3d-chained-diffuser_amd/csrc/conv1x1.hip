@@ -340,9 +340,22 @@ extern "C" int a3d_conv1x1_nslab(size_t M, int K, int N) {
   return c1_deep(K, N) ? conv1x1_deep_slabs(M, K, N) : 0;
 }
 
+// one launch of the <WN, KS, EP, RS> instance of the streaming kernel; its dynamic-LDS limit is raised once per instance
+typedef void (*c1_launch_fn)(dim3 grid, size_t lds, hipStream_t s, const void* x, const void* w, const float* in_scale, const float* in_shift,
+                             int in_relu, void* y, float* partial, size_t M, int N, const C1Epilogue& ep);
+template <int WN, int KS, bool EP, int RS>
+static void c1_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, const void* w, const float* in_scale, const float* in_shift,
+                      int in_relu, void* y, float* partial, size_t M, int N, const C1Epilogue& ep) {
+  static bool once = false;
+  if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WN, KS, EP, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; }
+  hipLaunchKernelGGL((conv1x1_stream_kernel<WN, KS, EP, RS>), grid, dim3(256), lds, s, (const unsigned short*)x, (const unsigned short*)w,
+                     in_scale, in_shift, in_relu, (unsigned short*)y, partial, (long long)M, N, ep);
+}
+static const C1Epilogue c1_no_epilogue{nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0};
+
 extern "C" int a3d_conv1x1_bn_fwd(const void* x, const void* w, const float* in_scale, const float* in_shift, int in_relu,
                                   void* y, float* partial, size_t M, int K, int N, void* stream) {
-  const bool stats_only = !y && partial && ((K == 64 && N == 256) || (K == 128 && N == 512));      // (a3d_conv1x1_bn_residual_serves)
+  const bool stats_only = !y && partial && a3d_conv1x1_bn_residual_serves(K, N);
   if (!x || !w || (!y && !stats_only) || M == 0 || K <= 0 || N <= 0 || !(c1_streams(K, N) || c1_deep(K, N)) || (in_scale && !in_shift) ||
       ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y) & 15) != 0)) {
     set_error("a3d_conv1x1_bn_fwd: bad argument (M=%zu K=%d N=%d; served shapes: K in {64, 128, 256}, N in {64, 128, 256 j}, weight block "
@@ -352,38 +365,21 @@ extern "C" int a3d_conv1x1_bn_fwd(const void* x, const void* w, const float* in_
   }
   hipStream_t s = (hipStream_t)stream;
   if (!c1_streams(K, N)) return conv1x1_deep_launch(x, w, in_scale, in_shift, in_relu, y, partial, M, K, N, s);
-  const unsigned short* xs = (const unsigned short*)x;
-  const unsigned short* ws = (const unsigned short*)w;
-  unsigned short* ys = (unsigned short*)y;
-  const int slabs = c1_slabs(M, K, N);
-  const size_t lds = c1_stream_lds(K, N);
-  const dim3 grid(slabs, N >= 256 ? N / 256 : 1);
-#define A3D_C1S(WNV, KSV)                                                                                                         \
-  do {                                                                                                                           \
-    static bool once = false;                                                                                                    \
-    if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WNV, KSV>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; } \
-    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV>), grid, dim3(256), lds, s, xs, ws, in_scale, in_shift, in_relu, ys, partial, (long long)M, N, C1Epilogue{nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0}); \
-  } while (0)
-#define A3D_C1N(WNV, KSV)                                                                                                         \
-  do {                                                                                                                           \
-    static bool once = false;                                                                                                    \
-    if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WNV, KSV, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; } \
-    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV, false, 2>), grid, dim3(256), lds, s, xs, ws, in_scale, in_shift, in_relu, ys, partial, (long long)M, N, C1Epilogue{nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0}); \
-  } while (0)
-  const int wn = c1_wn(N), ks = K / 32;
-  if (stats_only && ks == 2) A3D_C1N(4, 2);
-  else if (stats_only) A3D_C1N(4, 4);
-  else if (wn == 4 && ks == 2) A3D_C1S(4, 2);
-  else if (wn == 4 && ks == 4) A3D_C1S(4, 4);
-  else if (wn == 2 && ks == 2) A3D_C1S(2, 2);
-  else if (wn == 2 && ks == 4) A3D_C1S(2, 4);
-  else if (wn == 2 && ks == 8) A3D_C1S(2, 8);
-  else if (wn == 1 && ks == 2) A3D_C1S(1, 2);
-  else if (wn == 1 && ks == 4) A3D_C1S(1, 4);
-  else if (wn == 1 && ks == 8) A3D_C1S(1, 8);
-  else { set_error("a3d_conv1x1_bn_fwd: no streaming instance for K=%d N=%d", K, N); return A3D_ERR_ARG; }
-#undef A3D_C1S
-#undef A3D_C1N
+  c1_launch_fn launch = nullptr;
+  if (stats_only) launch = K == 64 ? c1_launch<4, 2, false, 2> : c1_launch<4, 4, false, 2>;      // RS == 2: the instances that store no y
+  else switch (c1_wn(N) * 16 + K / 32) {                         // (wn, ks)
+    case 4 * 16 + 2: launch = c1_launch<4, 2, false, 0>; break;
+    case 4 * 16 + 4: launch = c1_launch<4, 4, false, 0>; break;
+    case 2 * 16 + 2: launch = c1_launch<2, 2, false, 0>; break;
+    case 2 * 16 + 4: launch = c1_launch<2, 4, false, 0>; break;
+    case 2 * 16 + 8: launch = c1_launch<2, 8, false, 0>; break;
+    case 1 * 16 + 2: launch = c1_launch<1, 2, false, 0>; break;
+    case 1 * 16 + 4: launch = c1_launch<1, 4, false, 0>; break;
+    case 1 * 16 + 8: launch = c1_launch<1, 8, false, 0>; break;
+  }
+  if (!launch) { set_error("a3d_conv1x1_bn_fwd: no streaming instance for K=%d N=%d", K, N); return A3D_ERR_ARG; }
+  launch(dim3(c1_slabs(M, K, N), N >= 256 ? N / 256 : 1), c1_stream_lds(K, N), s, x, w, in_scale, in_shift, in_relu, y, partial, M, N,
+         c1_no_epilogue);
   return check_launch("a3d_conv1x1_bn_fwd");
 }
 
@@ -399,27 +395,18 @@ extern "C" int a3d_conv1x1_topdown_fwd(const void* x, const void* w, const float
               "H and W even with a top map, at most 2^32 rows, 0 < nbias <= N with a bias, 16-byte aligned operands)", images, H, W, K, N, nbias);
     return A3D_ERR_ARG;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int slabs = c1_slabs(M, K, N);
-  const size_t lds = c1_stream_lds(K, N);
-  const dim3 grid(slabs, 1);
   const C1Epilogue ep{bias, bias ? nbias : 0, (const unsigned short*)top, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0};
-#define A3D_C1E(WNV, KSV)                                                                                                         \
-  do {                                                                                                                           \
-    static bool once = false;                                                                                                    \
-    if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WNV, KSV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; } \
-    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV, true>), grid, dim3(256), lds, s, (const unsigned short*)x, (const unsigned short*)w, \
-                       (const float*)nullptr, (const float*)nullptr, 0, (unsigned short*)y, (float*)nullptr, (long long)M, N, ep);  \
-  } while (0)
-  const int wn = c1_wn(N), ks = K / 32;
-  if (wn == 2 && ks == 2) A3D_C1E(2, 2);
-  else if (wn == 2 && ks == 4) A3D_C1E(2, 4);
-  else if (wn == 2 && ks == 8) A3D_C1E(2, 8);
-  else if (wn == 1 && ks == 2) A3D_C1E(1, 2);
-  else if (wn == 1 && ks == 4) A3D_C1E(1, 4);
-  else if (wn == 1 && ks == 8) A3D_C1E(1, 8);
-  else { set_error("a3d_conv1x1_topdown_fwd: no streaming instance for K=%d N=%d", K, N); return A3D_ERR_ARG; }
-#undef A3D_C1E
+  c1_launch_fn launch = nullptr;
+  switch (c1_wn(N) * 16 + K / 32) {
+    case 2 * 16 + 2: launch = c1_launch<2, 2, true, 0>; break;
+    case 2 * 16 + 4: launch = c1_launch<2, 4, true, 0>; break;
+    case 2 * 16 + 8: launch = c1_launch<2, 8, true, 0>; break;
+    case 1 * 16 + 2: launch = c1_launch<1, 2, true, 0>; break;
+    case 1 * 16 + 4: launch = c1_launch<1, 4, true, 0>; break;
+    case 1 * 16 + 8: launch = c1_launch<1, 8, true, 0>; break;
+  }
+  if (!launch) { set_error("a3d_conv1x1_topdown_fwd: no streaming instance for K=%d N=%d", K, N); return A3D_ERR_ARG; }
+  launch(dim3(c1_slabs(M, K, N), 1), c1_stream_lds(K, N), (hipStream_t)stream, x, w, nullptr, nullptr, 0, y, nullptr, M, N, ep);
   return check_launch("a3d_conv1x1_topdown_fwd");
 }
 
@@ -436,20 +423,8 @@ extern "C" int a3d_conv1x1_bn_residual_fwd(const void* x, const void* w, const f
               M, K, N);
     return A3D_ERR_ARG;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int slabs = c1_slabs(M, K, N);
-  const size_t lds = c1_stream_lds(K, N, true);
-  const dim3 grid(slabs, N / 256);
   const C1Epilogue ep{nullptr, 0, nullptr, 0, 0, out_scale, out_shift, (const unsigned short*)res, res_scale, res_shift, relu ? 0.f : -INFINITY, round_conv ? 1 : 0};
-#define A3D_C1R(WNV, KSV)                                                                                                         \
-  do {                                                                                                                           \
-    static bool once = false;                                                                                                    \
-    if (!once) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<WNV, KSV, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); once = true; } \
-    hipLaunchKernelGGL((conv1x1_stream_kernel<WNV, KSV, false, 1>), grid, dim3(256), lds, s, (const unsigned short*)x, (const unsigned short*)w, \
-                       in_scale, in_shift, in_relu, (unsigned short*)y, (float*)nullptr, (long long)M, N, ep);                    \
-  } while (0)
-  if (K == 64) A3D_C1R(4, 2);
-  else A3D_C1R(4, 4);
-#undef A3D_C1R
+  const c1_launch_fn launch = K == 64 ? c1_launch<4, 2, false, 1> : c1_launch<4, 4, false, 1>;      // (wn, ks) = (4, 2) | (4, 4): the two served shapes
+  launch(dim3(c1_slabs(M, K, N), N / 256), c1_stream_lds(K, N, true), (hipStream_t)stream, x, w, in_scale, in_shift, in_relu, y, nullptr, M, N, ep);
   return check_launch("a3d_conv1x1_bn_residual_fwd");
 }

@@ -5,6 +5,7 @@ Reference classes mirrored: MultiheadCustomAttention (multihead_custom_attention
 FeedforwardLayer / RelativeCrossAttentionModule (layers.py:293-351), ParallelAttentionLayer / ParallelAttention / AdaLN
 (layers.py:7-290), torchvision's FeaturePyramidNetwork (third-party; restated) and a synthetic CLIP-RN50-shaped backbone.
 """
+import collections
 import math
 import os
 
@@ -533,23 +534,33 @@ def bn_scale_shift(x, bn, partial=None):
     return scale
 
 
-def conv1x1_bn(x, conv, in_scale=None, in_relu=False, want_stats=True):
-    """1x1 stride-1 convolution of a bf16 channels_last activation as the fused GEMM of csrc/conv1x1.hip: optional
-    BatchNorm-apply (+ ReLU) of the producer on the input (`in_scale` = bn_scale_shift of that layer), and the partial
-    statistics of the output for the BatchNorm that follows.  Returns (y, partial or None)."""
+def _conv1x1_operands(x, conv, in_scale, in_relu):
+    """The operand checks every 1x1 entry point shares and (M, K, Cout, pointer of the (Cout, K) weight, the (in_scale, in_shift,
+    in_relu) argument triple of the producer's BatchNorm-apply on the operand load)."""
     N, K, H, W = x.shape
     Cout = conv.weight.shape[0]
     assert x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
     assert conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.bias is None and conv.weight.dtype == torch.bfloat16
-    M = N * H * W
     w2 = conv.weight.reshape(Cout, K)
-    assert w2.is_contiguous()
-    y = torch.empty((N, Cout, H, W), device=x.device, dtype=torch.bfloat16, memory_format=torch.channels_last)
-    partial = None
+    assert w2.is_contiguous()                                      # (a view: the pointer is the weight's own)
+    pre = (None, None) if in_scale is None else (in_scale[0].data_ptr(), in_scale[1].data_ptr())
+    return N * H * W, K, Cout, w2.data_ptr(), pre + (1 if in_relu else 0,)
+
+
+def conv1x1_bn(x, conv, in_scale=None, in_relu=False, want_stats=True, store=True):
+    """1x1 stride-1 convolution of a bf16 channels_last activation as the fused GEMM of csrc/conv1x1.hip: optional
+    BatchNorm-apply (+ ReLU) of the producer on the input (`in_scale` = bn_scale_shift of that layer), and the partial
+    statistics of the output for the BatchNorm that follows.  Returns (y, partial or None).  store=False (the bottleneck's conv3
+    shapes, a3d_conv1x1_bn_residual_serves): the same kernel and the same sums of the bf16-rounded outputs, nothing stored
+    (a3d_conv1x1_bn_fwd with y = NULL) -- returns (None, partial)."""
+    M, K, Cout, w, pre = _conv1x1_operands(x, conv, in_scale, in_relu)
+    assert store or want_stats
+    y = partial = None
+    if store:
+        y = torch.empty((x.shape[0], Cout) + x.shape[2:], device=x.device, dtype=torch.bfloat16, memory_format=torch.channels_last)
     if want_stats:
         partial = torch.empty((O.L.load().a3d_conv1x1_nslab(M, K, Cout), 2, Cout), device=x.device, dtype=torch.float32)
-    O.L.call("a3d_conv1x1_bn_fwd", x.data_ptr(), w2.data_ptr(), None if in_scale is None else in_scale[0].data_ptr(),
-             None if in_scale is None else in_scale[1].data_ptr(), 1 if in_relu else 0, y.data_ptr(),
+    O.L.call("a3d_conv1x1_bn_fwd", x.data_ptr(), w, *pre, None if y is None else y.data_ptr(),
              None if partial is None else partial.data_ptr(), M, K, Cout, O.L.stream())
     return y, partial
 
@@ -558,37 +569,16 @@ def conv1x1_gram_stats(x, conv, in_scale=None, in_relu=False):
     """(1, 2, Cout) fp32 (sum, sum of squares) over rows of the OUTPUT of the 1x1 convolution `conv` on the bf16 channels_last x
     (with the producer's BatchNorm-apply `in_scale` folded in as conv1x1_bn folds it), computed from the K x K Gram matrix of its
     INPUT (csrc/bn_gram.hip): the record bn_scale_shift(partial=...) finalizes -- the statistics exist before the convolution runs."""
-    N, K, H, W = x.shape
-    Cout = conv.weight.shape[0]
-    assert x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last) and conv.weight.dtype == torch.bfloat16
-    M = N * H * W
-    w2 = conv.weight.reshape(Cout, K)
-    assert w2.is_contiguous()
+    M, K, Cout, w, pre = _conv1x1_operands(x, conv, in_scale, in_relu)
     dev, st = x.device, O.L.stream()
     nslab = O.L.load().a3d_bn_gram_nslab(M, K)
     part = torch.empty((nslab * (K * K + K),), device=dev, dtype=torch.float32)
     gpart, spart = part[:nslab * K * K], part[nslab * K * K:]
     work = torch.empty((K * K + K,), device=dev, dtype=torch.float64)
     stats = torch.empty((1, 2, Cout), device=dev, dtype=torch.float32)
-    O.L.call("a3d_bn_gram", x.data_ptr(), None if in_scale is None else in_scale[0].data_ptr(),
-             None if in_scale is None else in_scale[1].data_ptr(), 1 if in_relu else 0, gpart.data_ptr(), spart.data_ptr(), M, K, nslab, st)
-    O.L.call("a3d_bn_gram_stats", gpart.data_ptr(), spart.data_ptr(), nslab, w2.data_ptr(), K, Cout, work.data_ptr(), stats.data_ptr(), st)
+    O.L.call("a3d_bn_gram", x.data_ptr(), *pre, gpart.data_ptr(), spart.data_ptr(), M, K, nslab, st)
+    O.L.call("a3d_bn_gram_stats", gpart.data_ptr(), spart.data_ptr(), nslab, w, K, Cout, work.data_ptr(), stats.data_ptr(), st)
     return stats
-
-
-def conv1x1_stats_only(x, conv, in_scale=None, in_relu=False):
-    """the `partial` statistics conv1x1_bn would return for the bottleneck's conv3, WITHOUT its output: the same kernel, the same sums
-    of the bf16-rounded outputs, nothing stored (a3d_conv1x1_bn_fwd with y = NULL)."""
-    N, K, H, W = x.shape
-    Cout = conv.weight.shape[0]
-    assert x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last) and conv.weight.dtype == torch.bfloat16
-    M = N * H * W
-    w2 = conv.weight.reshape(Cout, K)
-    assert w2.is_contiguous()
-    partial = torch.empty((O.L.load().a3d_conv1x1_nslab(M, K, Cout), 2, Cout), device=x.device, dtype=torch.float32)
-    O.L.call("a3d_conv1x1_bn_fwd", x.data_ptr(), w2.data_ptr(), None if in_scale is None else in_scale[0].data_ptr(),
-             None if in_scale is None else in_scale[1].data_ptr(), 1 if in_relu else 0, None, partial.data_ptr(), M, K, Cout, O.L.stream())
-    return partial
 
 
 def conv1x1_bn_residual(x, conv, out_scale, residual, in_scale=None, in_relu=False, residual_scale=None, relu=True, out=None,
@@ -596,31 +586,31 @@ def conv1x1_bn_residual(x, conv, out_scale, residual, in_scale=None, in_relu=Fal
     """relu?(bn(conv(f(x))) + r) in ONE launch (a3d_conv1x1_bn_residual_fwd): the 1x1 convolution of conv1x1_bn with the BatchNorm-apply
     of its OWN output (`out_scale` = bn_scale_shift of conv1x1_gram_stats), the residual add (`residual_scale`: the folded BatchNorm of
     the downsample branch) and the ReLU as its epilogue, one rounding from the fp32 accumulator; the raw convolution output is never
-    written.  round_conv: the accumulator is rounded to bf16 first -- with `out_scale` from conv1x1_stats_only the result is
+    written.  round_conv: the accumulator is rounded to bf16 first -- with `out_scale` from conv1x1_bn(store=False) the result is
     conv1x1_bn + bn_act's, bit for bit.  out: a preallocated tensor for the result."""
-    N, K, H, W = x.shape
-    Cout = conv.weight.shape[0]
-    assert x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
-    assert residual.shape == (N, Cout, H, W) and residual.dtype == torch.bfloat16 and residual.is_contiguous(memory_format=torch.channels_last)
-    w2 = conv.weight.reshape(Cout, K)
-    assert w2.is_contiguous()
+    M, K, Cout, w, pre = _conv1x1_operands(x, conv, in_scale, in_relu)
+    assert residual.shape == (x.shape[0], Cout) + x.shape[2:] and residual.dtype == torch.bfloat16 and \
+        residual.is_contiguous(memory_format=torch.channels_last)
     if out is not None:
         assert out.shape == residual.shape and out.dtype == torch.bfloat16 and out.is_contiguous(memory_format=torch.channels_last)
     y = out if out is not None else torch.empty_like(residual)
-    O.L.call("a3d_conv1x1_bn_residual_fwd", x.data_ptr(), w2.data_ptr(), None if in_scale is None else in_scale[0].data_ptr(),
-             None if in_scale is None else in_scale[1].data_ptr(), 1 if in_relu else 0, out_scale[0].data_ptr(), out_scale[1].data_ptr(),
+    O.L.call("a3d_conv1x1_bn_residual_fwd", x.data_ptr(), w, *pre, out_scale[0].data_ptr(), out_scale[1].data_ptr(),
              residual.data_ptr(), None if residual_scale is None else residual_scale[0].data_ptr(),
              None if residual_scale is None else residual_scale[1].data_ptr(), 1 if relu else 0, 1 if round_conv else 0, y.data_ptr(),
-             N * H * W, K, Cout, O.L.stream())
+             M, K, Cout, O.L.stream())
     return y
+
+
+def _conv3x3_ok(conv, Cin, H, W):
+    """the structure of `conv` and the (Cin, H, W) of its input are what a3d_conv3x3_bn_fwd serves"""
+    return bool(conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and
+                conv.groups == 1 and conv.bias is None and O.L.load().a3d_conv3x3_serves(Cin, conv.out_channels, H, W))
 
 
 def conv3x3_serves(x, conv):
     """the 3x3 convolution `conv` on the bf16 channels_last map x is one a3d_conv3x3_bn_fwd serves (stride 1, padding 1, no bias,
     32 -> 32 / 32 -> 64 / 64 -> 64 channels, H % 8 == 0, W % 32 == 0)"""
-    return bool(conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and
-                conv.groups == 1 and conv.bias is None and conv.weight.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and
-                O.L.load().a3d_conv3x3_serves(x.shape[1], conv.weight.shape[0], x.shape[2], x.shape[3]))
+    return conv.weight.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and _conv3x3_ok(conv, x.shape[1], x.shape[2], x.shape[3])
 
 
 def conv3x3_bn(x, conv, in_scale=None, in_relu=False, want_stats=True):
@@ -649,9 +639,8 @@ FUSED_STEM = os.environ.get("A3D_FUSED_STEM", "1") == "1"
 def stem_serves(x, conv, normalize):
     """conv1 of the CLIP stem on the raw fp32 images x with ClipNormalize in front is one a3d_stem_conv_bn_fwd serves"""
     return bool(FUSED_STEM and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.is_contiguous() and
-                isinstance(normalize, ClipNormalize) and isinstance(conv, nn.Conv2d) and conv.in_channels == 3 and conv.out_channels == 32 and
-                conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.bias is None and
-                conv.weight.dtype == torch.bfloat16 and O.L.load().a3d_stem_conv_nslab(x.shape[0], x.shape[2], x.shape[3]) > 0)
+                isinstance(normalize, ClipNormalize) and conv.weight.dtype == torch.bfloat16 and
+                _stem_conv_ok(conv, x.shape[0], x.shape[2], x.shape[3]))
 
 
 def stem_conv_bn(x, conv, normalize, want_stats=True):
@@ -706,128 +695,251 @@ def bn_act(x, bn, relu=True, residual=None, pool=False, keep_full=True, partial=
     return y, yp
 
 
-def _pool2_ok(m, t):
-    """m is the nn.AvgPool2d(2) of a stride-2 CLIP bottleneck and t has even spatial size (else: torch's pool)."""
-    return isinstance(m, nn.AvgPool2d) and m.kernel_size in (2, (2, 2)) and t.shape[-1] % 2 == 0 and t.shape[-2] % 2 == 0
+def _is_pool(m, k):
+    return isinstance(m, nn.AvgPool2d) and m.kernel_size in (k, (k, k))
+
+
+def _pool2_ok(m, hw):
+    """m is the nn.AvgPool2d(2) of a stride-2 CLIP bottleneck and the map has even spatial size hw (else: torch's pool)."""
+    return _is_pool(m, 2) and hw[0] % 2 == 0 and hw[1] % 2 == 0
+
+
+def _out_hw(m, hw):
+    """spatial size of module m's output for an input of size hw (nn.Conv2d, nn.AvgPool2d or nn.Identity)"""
+    if isinstance(m, nn.Identity):
+        return hw
+    k, s, p = ((v, v) if isinstance(v, int) else v for v in (m.kernel_size, m.stride, m.padding))
+    return (hw[0] + 2 * p[0] - k[0]) // s[0] + 1, (hw[1] + 2 * p[1] - k[1]) // s[1] + 1
+
+
+# The stem's route.  conv1: "stem_conv" (a3d_stem_conv_bn_fwd on the raw images: normalisation + convolution + statistics) | "library";
+# conv2, conv3: "fused" (a3d_conv3x3_bn_fwd, the producer's BatchNorm on its operand load) | "library" (a3d_bn_apply + the library);
+# stats: per BatchNorm "epilogue" (the producing kernel left them) | "bn_stats" | "none" (eval); final: "bn_apply_pool2" (res1 and its
+# pooled map in one launch) | "bn_apply" (+ torch's pool)
+StemRoute = collections.namedtuple("StemRoute", ("conv1", "conv2", "conv3", "stats", "final"))
+
+
+class BlockRoute(collections.namedtuple("BlockRoute", (
+        "name", "conv1", "stats1", "conv2", "stats2", "bn2", "conv3", "stats3", "ds_input", "ds_conv", "ds_stats", "ds_bn", "final", "writes"))):
+    """One bottleneck's route.
+      name      "layer2[0]"
+      conv1     "gemm" (a3d_conv1x1_bn_fwd) | "library"
+      conv2     "fused" (a3d_conv3x3_bn_fwd with bn1 + ReLU on its operand load) | "library" (a3d_bn_apply + the library)
+      bn2       "conv3_prologue" (rides on conv3's operand load) | "bn_apply_pool2" (the pooled map only) | "bn_apply+torch_pool" | "bn_apply"
+      conv3     "residual" (a3d_conv1x1_bn_residual_fwd; its prologue is bn2 == "conv3_prologue", none on an already pooled input) |
+                "gemm" (a3d_conv1x1_bn_fwd with statistics) | "library"
+      stats1, stats2, ds_stats   "epilogue" (the producing kernel left them) | "bn_stats" | "none" (eval)
+      stats3    those, or on the residual route "stats_pass" (a3d_conv1x1_bn_fwd that stores nothing) | "gram" (a3d_bn_gram + a3d_bn_gram_stats)
+      ds_input  None (no downsample branch) | "producer_pooled" (the previous block's a3d_bn_apply_pool2 emitted it) | "pool2" (pool-only
+                a3d_bn_apply_pool2) | "identity" (AvgPool2d(1)) | "torch_pool"
+      ds_conv   None | "gemm" | "library"
+      ds_bn     None | "folded" (into the final apply or epilogue) | "materialised" (a3d_bn_apply of its own)
+      final     "conv3_epilogue" (round-first: bit for bit a3d_bn_apply's) | "conv3_epilogue_gram" (one rounding from the accumulator) |
+                "bn_apply" | "bn_apply_pool2" (also emits the pooled map for the next block's downsample branch)
+      writes    "res2" .. "res5" for a layer's last block, else None"""
+    __slots__ = ()
+
+    def launches(self):
+        """entry-point names the block launches, in order"""
+        scale = lambda stats: ["a3d_bn_stats"] * (stats == "bn_stats") + ["a3d_bn_finalize"]
+        gemm = lambda route: ["a3d_conv1x1_bn_fwd"] * (route == "gemm")
+        seq = gemm(self.conv1) + scale(self.stats1) + ["a3d_conv3x3_bn_fwd" if self.conv2 == "fused" else "a3d_bn_apply"] + scale(self.stats2)
+        if self.bn2 != "conv3_prologue":
+            seq += ["a3d_bn_apply_pool2" if self.bn2 == "bn_apply_pool2" else "a3d_bn_apply"]
+        seq += gemm(self.conv3)
+        if self.ds_input is not None:
+            seq += ["a3d_bn_apply_pool2"] * (self.ds_input == "pool2") + gemm(self.ds_conv) + scale(self.ds_stats)
+            seq += ["a3d_bn_apply"] * (self.ds_bn == "materialised")
+        if self.conv3 == "residual":
+            stats = {"stats_pass": ["a3d_conv1x1_bn_fwd"], "gram": ["a3d_bn_gram", "a3d_bn_gram_stats"], "none": []}[self.stats3]
+            return seq + stats + ["a3d_bn_finalize", "a3d_conv1x1_bn_residual_fwd"]
+        return seq + scale(self.stats3) + ["a3d_" + self.final]
+
+
+class BackbonePlan(collections.namedtuple("BackbonePlan", ("stem", "blocks", "bns"))):
+    """stem: StemRoute; blocks: one BlockRoute per bottleneck in execution order; bns: the dotted names of the BatchNorm modules the
+    forward passes through (their num_batches_tracked advance in training mode)"""
+    __slots__ = ()
+
+    def launches(self):
+        """entry-point names of the whole forward, in order (conv1 == "library": from the normalised bf16 image on)"""
+        s, scale = self.stem, lambda stats: ["a3d_bn_stats"] * (stats == "bn_stats") + ["a3d_bn_finalize"]
+        seq = ["a3d_stem_conv_bn_fwd"] * (s.conv1 == "stem_conv")
+        for route, stats in zip((s.conv2, s.conv3), s.stats):
+            seq += scale(stats) + ["a3d_conv3x3_bn_fwd" if route == "fused" else "a3d_bn_apply"]
+        seq += scale(s.stats[2]) + ["a3d_" + s.final]
+        return seq + [e for b in self.blocks for e in b.launches()]
+
+
+def _stem_conv_ok(conv, images, H, W):
+    """conv is the CLIP stem's strided conv1 and a3d_stem_conv_bn_fwd serves (images, H, W)"""
+    return bool(isinstance(conv, nn.Conv2d) and conv.in_channels == 3 and conv.out_channels == 32 and conv.kernel_size == (3, 3) and
+                conv.stride == (2, 2) and conv.padding == (1, 1) and conv.bias is None and O.L.load().a3d_stem_conv_nslab(images, H, W) > 0)
+
+
+def backbone_plan(bb, images, H, W, fused_stem=None):
+    """Which launches serve a fused_frozen_backbone_forward call, from host values alone: the SyntheticCLIPResNet50 `bb` (only its
+    structure and each BatchNorm's `training` bit are read: it may live on the CPU) on `images` raw images of H x W.  The module
+    switches FUSED_CONV1X1, FUSED_CONV3X3, FUSED_CONV3_RESIDUAL, FOLD_DOWNSAMPLE_BN and (unless the caller says whether the stem kernel
+    ran: fused_stem) FUSED_STEM are read here, at call time.  Assumes what run_frozen_backbone establishes (bf16 convolution weights,
+    channels_last bf16 maps); nothing is allocated or launched -- the library answers the shape queries a3d_stem_conv_nslab,
+    a3d_conv3x3_serves, a3d_conv1x1_streams (which follows a3d_conv1x1_deep_mode) and a3d_conv1x1_bn_residual_serves on the host."""
+    fused_stem = FUSED_STEM if fused_stem is None else fused_stem
+    fuse1, fuse3, res_mode, fold = FUSED_CONV1X1, FUSED_CONV3X3, FUSED_CONV3_RESIDUAL, FOLD_DOWNSAMPLE_BN
+    lib = O.L.load()
+    stats = lambda own, bn: "none" if not bn.training else ("epilogue" if own else "bn_stats")
+    plain1x1 = lambda m: m.kernel_size == (1, 1) and m.stride == (1, 1)
+    # the route predicates: m a convolution, hw the spatial size of its input
+    c3x3 = lambda m, hw: "fused" if fuse3 and _conv3x3_ok(m, m.in_channels, hw[0], hw[1]) else "library"
+    c1x1 = lambda m: "gemm" if fuse1 and plain1x1(m) and lib.a3d_conv1x1_streams(m.in_channels, m.out_channels) else "library"
+    res_ok = lambda m: bool(res_mode and fuse1 and plain1x1(m) and m.bias is None and
+                            lib.a3d_conv1x1_bn_residual_serves(m.in_channels, m.out_channels))
+
+    conv1 = "stem_conv" if fused_stem and _stem_conv_ok(bb.conv1, images, H, W) else "library"
+    hw = _out_hw(bb.conv1, (H, W))
+    conv2 = c3x3(bb.conv2, hw)
+    hw = _out_hw(bb.conv2, hw)
+    conv3 = c3x3(bb.conv3, hw)
+    hw = _out_hw(bb.conv3, hw)
+    pool2 = _pool2_ok(bb.avgpool, hw)
+    stem = StemRoute(conv1, conv2, conv3, (stats(conv1 == "stem_conv", bb.bn1), stats(conv2 == "fused", bb.bn2), stats(conv3 == "fused", bb.bn3)),
+                     "bn_apply_pool2" if pool2 else "bn_apply")
+    hw = _out_hw(bb.avgpool, hw)
+
+    bns = ["bn1", "bn2", "bn3"]
+    named = [("layer%d" % (li + 1), bi, blk) for li in range(4) for bi, blk in enumerate(getattr(bb, "layer%d" % (li + 1)))]
+    routes, have_pooled = [], False                    # have_pooled: the producer of the block's input also emitted AvgPool2d(2) of it
+    for i, (layer, bi, blk) in enumerate(named):
+        nxt = named[i + 1][2] if i + 1 < len(named) else None
+        r1 = c1x1(blk.conv1)
+        hw1 = _out_hw(blk.conv1, hw)
+        r2 = c3x3(blk.conv2, hw1)
+        hw2 = _out_hw(blk.conv2, hw1)
+        no_pool = isinstance(blk.avgpool, nn.Identity) or _is_pool(blk.avgpool, 1)
+        hw3 = hw2 if no_pool else _out_hw(blk.avgpool, hw2)             # conv3's input and the block's output
+        # the next block's downsample branch wants the pooled output: the final a3d_bn_apply_pool2 emits it, so conv3 keeps its raw map
+        pooled_next = nxt is not None and nxt.downsample is not None and _pool2_ok(nxt.downsample[0], hw3)
+        r3 = "residual" if not pooled_next and res_ok(blk.conv3) else c1x1(blk.conv3)
+        if no_pool and r3 != "library":
+            bn2 = "conv3_prologue"
+        else:
+            bn2 = "bn_apply_pool2" if _pool2_ok(blk.avgpool, hw2) else "bn_apply" if no_pool else "bn_apply+torch_pool"
+        if r3 == "residual":
+            st3 = "none" if not blk.bn3.training else "gram" if res_mode == "gram" else "stats_pass"
+            final = "conv3_epilogue_gram" if res_mode == "gram" else "conv3_epilogue"
+        else:
+            st3, final = stats(r3 == "gemm", blk.bn3), "bn_apply_pool2" if pooled_next else "bn_apply"
+        ds_input = ds_conv = ds_stats = ds_bn = None
+        if blk.downsample is not None:
+            dpool, dconv, dbn = blk.downsample
+            ds_input = "producer_pooled" if have_pooled else "pool2" if _pool2_ok(dpool, hw) else "identity" if _is_pool(dpool, 1) else "torch_pool"
+            ds_conv = c1x1(dconv)
+            ds_stats = stats(ds_conv == "gemm", dbn)
+            ds_bn = "folded" if fold and final != "bn_apply_pool2" else "materialised"       # (the pooled apply takes a materialised residual)
+            bns.append("%s.%d.downsample.2" % (layer, bi))
+        bns += ["%s.%d.bn%d" % (layer, bi, j) for j in (1, 2, 3)]
+        last = bi == len(getattr(bb, layer)) - 1
+        routes.append(BlockRoute("%s[%d]" % (layer, bi), r1, stats(r1 == "gemm", blk.bn1), r2, stats(r2 == "fused", blk.bn2), bn2, r3, st3,
+                                 ds_input, ds_conv, ds_stats, ds_bn, final, "res%d" % (int(layer[-1]) + 1) if last else None))
+        hw, have_pooled = hw3, final == "bn_apply_pool2"
+    return BackbonePlan(stem, tuple(routes), tuple(bns))
 
 
 def fused_frozen_backbone_forward(bb, x, stem=None, out=None):
     """SyntheticCLIPResNet50.forward with MIOpen bf16 NHWC convolutions and the fused BatchNorm of vision.hip.
     Same dataflow as the module's own forward (CLIP ModifiedResNet, model/utils/clip.py:28-43); every AvgPool2d(2) is
     folded into the BatchNorm-apply kernel that produces its input (the block output also feeds the next block's
-    downsample branch pooled, so that kernel emits both).  out: {res1..res5} preallocated maps the five returned maps are written
-    into by the kernels that produce them (no copy)."""
+    downsample branch pooled, so that kernel emits both).  Runs what backbone_plan decides for its input: every step below
+    dispatches on the record's strings.  x: the normalised bf16 channels_last images, or None with stem = (raw output of conv1,
+    partial statistics) from stem_conv_bn.  out: {res1..res5} preallocated maps the five returned maps are written into by the
+    kernels that produce them (no copy)."""
+    c1, p1 = stem if stem is not None else (None, None)
+    images, H, W = (c1.shape[0], 2 * c1.shape[2], 2 * c1.shape[3]) if stem is not None else (x.shape[0], x.shape[2], x.shape[3])
+    plan = backbone_plan(bb, images, H, W, fused_stem=stem is not None)
+    assert (plan.stem.conv1 == "stem_conv") == (stem is not None)
+    # what the plan assumes of its input and of the frozen weights (run_frozen_backbone converts them once)
+    src = c1 if stem is not None else x
+    assert src.dtype == torch.bfloat16 and src.is_contiguous(memory_format=torch.channels_last)
+    assert all(m.weight.dtype == torch.bfloat16 for m in bb.modules() if isinstance(m, nn.Conv2d))
+    maps = {} if out is None else out
     conv = lambda m, t: F.conv2d(t, m.weight, None, m.stride, m.padding)
-    fuse3 = FUSED_CONV3X3
-    o_ = (lambda k: None) if out is None else (lambda k, _maps=out: _maps[k])        # (`out` is rebound as a local further down)
 
-    def conv3(m, t, bn_in, p_in, want_stats):
+    def conv3x3(route, m, t, bn_in, p_in, want_stats):
         """3x3 convolution m of relu(bn_in(t)) (t = the raw output of the previous convolution, p_in its partial statistics or
-        None) + the partial statistics of its own output: one a3d_conv3x3_bn_fwd where it serves the shape -- relu(bn_in(t)) is
-        then never materialised -- else BatchNorm-apply + MIOpen"""
-        if fuse3 and conv3x3_serves(t, m):
+        None) + the partial statistics of its own output: one a3d_conv3x3_bn_fwd -- relu(bn_in(t)) is then never materialised --
+        or BatchNorm-apply + MIOpen"""
+        if route == "fused":
             return conv3x3_bn(t, m, in_scale=bn_scale_shift(t, bn_in, p_in), in_relu=True, want_stats=want_stats)
         return conv(m, bn_act(t, bn_in, partial=p_in)), None
 
-    # stem: (raw output of conv1, partial statistics) from a3d_stem_conv_bn_fwd (normalisation + convolution + statistics in one
-    # launch, stem_conv_bn), else the library's convolution of the normalised bf16 image x
-    c1, p1 = stem if stem is not None else (conv(bb.conv1, x), None)
-    c2, p2 = conv3(bb.conv2, c1, bb.bn1, p1, bb.bn2.training)
-    c3, p3 = conv3(bb.conv3, c2, bb.bn2, p2, bb.bn3.training)
-    if _pool2_ok(bb.avgpool, c3):
-        x0, x = bn_act(c3, bb.bn3, pool=True, partial=p3, out=o_("res1"))
-    else:
-        x0 = bn_act(c3, bb.bn3, partial=p3, out=o_("res1"))
-        x = bb.avgpool(x0)
-    outs = [x0]
-    bns = [bb.bn1, bb.bn2, bb.bn3]
-    blocks = [blk for layer in (bb.layer1, bb.layer2, bb.layer3, bb.layer4) for blk in layer]
-    last_of_layer = {id(layer[-1]) for layer in (bb.layer1, bb.layer2, bb.layer3, bb.layer4)}
-    x_pooled = None                                    # AvgPool2d(2)(x), when the producer of x already emitted it
-    fuse = FUSED_CONV1X1
-
-    def fused_ok(m, t):
-        """the 1x1 convolution m on input t goes through a3d_conv1x1_bn_fwd (the shapes its streaming kernel serves)"""
-        return bool(fuse and m.kernel_size == (1, 1) and m.stride == (1, 1) and
-                    O.L.load().a3d_conv1x1_streams(t.shape[1], m.weight.shape[0]))
-
-    def conv1(m, t, **kw):
+    def conv1x1(route, m, t, **kw):
         """1x1 convolution + the partial statistics of its output (None on the MIOpen path)"""
-        if fused_ok(m, t):
-            return conv1x1_bn(t, m, **kw)
-        return conv(m, t), None
+        return conv1x1_bn(t, m, **kw) if route == "gemm" else (conv(m, t), None)
 
-    def res_ok(m, t):
-        """conv3 m on the bf16 channels_last t goes through a3d_conv1x1_bn_residual_fwd: bn3 + add + ReLU in its epilogue"""
-        return bool(FUSED_CONV3_RESIDUAL and fuse and m.kernel_size == (1, 1) and m.stride == (1, 1) and m.bias is None and
-                    m.weight.dtype == torch.bfloat16 and t.dtype == torch.bfloat16 and t.is_contiguous(memory_format=torch.channels_last) and
-                    O.L.load().a3d_conv1x1_bn_residual_serves(t.shape[1], m.weight.shape[0]))
-
-    for bi, blk in enumerate(blocks):
-        c1, p1 = conv1(blk.conv1, x, want_stats=blk.bn1.training)
-        c2, p2 = conv3(blk.conv2, c1, blk.bn1, p1, blk.bn2.training)
-        no_pool = isinstance(blk.avgpool, nn.Identity) or (isinstance(blk.avgpool, nn.AvgPool2d) and blk.avgpool.kernel_size in (1, (1, 1)))
-        nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
-        # (the pooled map a layer's last block also emits still comes from a3d_bn_apply_pool2: those blocks keep the raw conv3 map)
-        pooled_next = lambda t: nxt is not None and nxt.downsample is not None and _pool2_ok(nxt.downsample[0], t)   # t: conv3's input
-        o3 = p3 = a3 = a3_scale = None                   # a3 (+ a3_scale): conv3's input (+ its pending BatchNorm-apply) on the fused-residual route
-        if no_pool and not pooled_next(c2) and res_ok(blk.conv3, c2):
+    s = plan.stem
+    if stem is None:
+        c1 = conv(bb.conv1, x)
+    c2, p2 = conv3x3(s.conv2, bb.conv2, c1, bb.bn1, p1, bb.bn2.training)
+    c3, p3 = conv3x3(s.conv3, bb.conv3, c2, bb.bn2, p2, bb.bn3.training)
+    if s.final == "bn_apply_pool2":
+        x0, x = bn_act(c3, bb.bn3, pool=True, partial=p3, out=maps.get("res1"))
+    else:
+        x0 = bn_act(c3, bb.bn3, partial=p3, out=maps.get("res1"))
+        x = bb.avgpool(x0)
+    outs = {"res1": x0}
+    x_pooled = None                                    # AvgPool2d(2)(x), when the producer of x already emitted it
+    blocks = [blk for layer in (bb.layer1, bb.layer2, bb.layer3, bb.layer4) for blk in layer]
+    for r, blk in zip(plan.blocks, blocks):
+        c1, p1 = conv1x1(r.conv1, blk.conv1, x, want_stats=blk.bn1.training)
+        c2, p2 = conv3x3(r.conv2, blk.conv2, c1, blk.bn1, p1, blk.bn2.training)
+        # a3 (+ a3_scale): conv3's input (+ its pending BatchNorm-apply, which then rides on conv3's operand load: c2 is never rewritten)
+        a3_scale = None
+        if r.bn2 == "conv3_prologue":
             a3, a3_scale = c2, bn_scale_shift(c2, blk.bn2, p2)
-        elif no_pool and fused_ok(blk.conv3, c2):
-            # BatchNorm-apply + ReLU of bn2 ride on conv3's operand load: c2 is never rewritten
-            o3, p3 = conv1x1_bn(c2, blk.conv3, in_scale=bn_scale_shift(c2, blk.bn2, p2), in_relu=True, want_stats=blk.bn3.training)
+        elif r.bn2 == "bn_apply_pool2":
+            a3 = bn_act(c2, blk.bn2, pool=True, keep_full=False, partial=p2)[1]
         else:
-            if _pool2_ok(blk.avgpool, c2):
-                out = bn_act(c2, blk.bn2, pool=True, keep_full=False, partial=p2)[1]
-            else:
-                out = blk.avgpool(bn_act(c2, blk.bn2, partial=p2))
-            if not pooled_next(out) and res_ok(blk.conv3, out):
-                a3 = out                                 # already normalised and pooled: no prologue
-            else:
-                o3, p3 = conv1(blk.conv3, out, want_stats=blk.bn3.training)
-        if blk.downsample is not None:
-            dpool = blk.downsample[0]
-            if x_pooled is not None:
+            a3 = blk.avgpool(bn_act(c2, blk.bn2, partial=p2))
+        pre = dict(in_scale=a3_scale, in_relu=a3_scale is not None)
+        if r.conv3 != "residual":
+            o3, p3 = conv1x1(r.conv3, blk.conv3, a3, want_stats=blk.bn3.training, **pre)
+        idn, idn_scale = x, None
+        if r.ds_input is not None:
+            dpool, dconv, dbn = blk.downsample
+            if r.ds_input == "producer_pooled":
                 xin = x_pooled
-            elif _pool2_ok(dpool, x):
+            elif r.ds_input == "pool2":
                 xin = bn_act(x, None, relu=False, pool=True, keep_full=False)[1]
-            elif isinstance(dpool, nn.AvgPool2d) and dpool.kernel_size in (1, (1, 1)):
-                xin = x                                # AvgPool2d(1) is the identity
             else:
-                xin = dpool(x)
-            cd, pd = conv1(blk.downsample[1], xin, want_stats=blk.downsample[2].training)
-            bns.append(blk.downsample[2])
-        want_pooled = a3 is None and pooled_next(o3)
-        idn_scale = None
-        if blk.downsample is None:
-            idn = x
-        elif FOLD_DOWNSAMPLE_BN and not want_pooled:
-            # the branch's BatchNorm rides in the block's final apply: bn_d(cd) is never materialised
-            idn, idn_scale = cd, bn_scale_shift(cd, blk.downsample[2], pd)
-        else:
-            idn = bn_act(cd, blk.downsample[2], relu=False, partial=pd)
-        o_x = o_("res%d" % (len(outs) + 1)) if id(blk) in last_of_layer else None      # a layer's last block writes the returned map
-        if a3 is not None:
+                xin = x if r.ds_input == "identity" else dpool(x)
+            cd, pd = conv1x1(r.ds_conv, dconv, xin, want_stats=dbn.training)
+            if r.ds_bn == "folded":
+                # the branch's BatchNorm rides in the block's final apply: bn_d(cd) is never materialised
+                idn, idn_scale = cd, bn_scale_shift(cd, dbn, pd)
+            else:
+                idn = bn_act(cd, dbn, relu=False, partial=pd)
+        o_x, x_pooled = maps.get(r.writes), None               # a layer's last block writes the returned map
+        if r.conv3 == "residual":
             # bn3's statistics first (none in eval mode) -- the sums of the bf16-rounded conv3 outputs from a pass of the GEMM that stores
             # nothing, or ("gram") of the unrounded product from the Gram matrix of conv3's input --, then conv3 + bn3 + add + ReLU in
             # one launch: the raw conv3 map is never written
-            gram = FUSED_CONV3_RESIDUAL == "gram"
             st3 = None
-            if blk.bn3.training:
-                st3 = (conv1x1_gram_stats if gram else conv1x1_stats_only)(a3, blk.conv3, in_scale=a3_scale, in_relu=a3_scale is not None)
+            if r.stats3 == "gram":
+                st3 = conv1x1_gram_stats(a3, blk.conv3, **pre)
+            elif r.stats3 == "stats_pass":
+                st3 = conv1x1_bn(a3, blk.conv3, store=False, **pre)[1]
             sc3 = bn_scale_shift(idn, blk.bn3, partial=st3)        # (idn has conv3's output shape: rows and channels)
-            x, x_pooled = conv1x1_bn_residual(a3, blk.conv3, sc3, idn, in_scale=a3_scale, in_relu=a3_scale is not None,
-                                              residual_scale=idn_scale, relu=True, out=o_x, round_conv=not gram), None
-        elif want_pooled:
+            x = conv1x1_bn_residual(a3, blk.conv3, sc3, idn, residual_scale=idn_scale, relu=True, out=o_x,
+                                    round_conv=r.final == "conv3_epilogue", **pre)
+        elif r.final == "bn_apply_pool2":
             x, x_pooled = bn_act(o3, blk.bn3, relu=True, residual=idn, pool=True, partial=p3, out=o_x)
         else:
-            x, x_pooled = bn_act(o3, blk.bn3, relu=True, residual=idn, partial=p3, residual_scale=idn_scale, out=o_x), None
-        bns += [blk.bn1, blk.bn2, blk.bn3]
-        if id(blk) in last_of_layer:
-            outs.append(x)
+            x = bn_act(o3, blk.bn3, relu=True, residual=idn, partial=p3, residual_scale=idn_scale, out=o_x)
+        if r.writes is not None:
+            outs[r.writes] = x
     if bb.training:
-        torch._foreach_add_([b.num_batches_tracked for b in bns], 1)
-    return dict(zip(["res1", "res2", "res3", "res4", "res5"], outs))
+        torch._foreach_add_([bb.get_submodule(n).num_batches_tracked for n in plan.bns], 1)
+    return outs
 
 
 FUSED_BN = os.environ.get("A3D_FUSED_BN", "1") == "1"
