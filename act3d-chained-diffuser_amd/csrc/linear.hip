@@ -12,6 +12,7 @@
 #include "a3d_common.h"
 #include "../../include/act3d_hip.h"
 #include <stdlib.h>
+#include <string.h>
 
 namespace a3d {
 
@@ -271,6 +272,68 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
   else db[n] += v;
 }
 
+// The deferred second stage of a whole backward pass: ONE launch over a device-resident table of A3dGradReduceRec.  Records that
+// add into the same destination (tied weights, one record per pyramid level) sit next to each other behind a leader whose
+// group_len counts them; a workgroup serves one (leader, 64-output chunk) pair, found by walking the leaders.  Per output: the
+// slabs of a record in a fixed 16-way interleave (as wgrad_reduce_kernel), the records of a group in table order, then ONE add
+// into the destination -- no atomics, the same bits on every run.
+__global__ __launch_bounds__(1024) void grad_reduce_table_kernel(const A3dGradReduceRec* __restrict__ table, int nrec) {
+  __shared__ float red[2][16][64];
+  int bid = blockIdx.x, r = 0, chunk = -1;
+  while (r < nrec) {
+    const int nch = (table[r].count + 63) >> 6;
+    if (bid < nch) { chunk = bid; break; }
+    bid -= nch;
+    r += max(table[r].group_len, 1);
+  }
+  if (chunk < 0) return;                                           // the whole workgroup: no barrier is skipped by a part of it
+  const int lane = threadIdx.x & 63, zg = threadIdx.x >> 6;
+  const int idx = chunk * 64 + lane;
+  const A3dGradReduceRec lead = table[r];
+  const int members = min(max(lead.group_len, 1), nrec - r);
+  float v = 0.f;
+  for (int g = 0; g < members; ++g) {
+    const float* __restrict__ partial = table[r + g].partial;
+    const int nsplit = table[r + g].nsplit;
+    const size_t stride = (size_t)table[r + g].slab_stride;
+    // slabs zg, zg + 16, ...: eight independent loads in flight per thread (333 slabs: three round trips, not eleven)
+    float a[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[u] = 0.f;
+    if (idx < lead.count) {
+      int z = zg;
+      for (; z + 7 * 16 < nsplit; z += 8 * 16) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a[u] += partial[(size_t)(z + u * 16) * stride + idx];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (z + u * 16 < nsplit) a[u] += partial[(size_t)(z + u * 16) * stride + idx];
+    }
+    // two LDS buffers in turn: one barrier per record (wave 0 has left buffer g & 1 before anybody passes the next barrier)
+    red[g & 1][zg][lane] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    __syncthreads();
+    if (zg == 0) {
+      float t = 0.f;
+#pragma unroll
+      for (int u = 0; u < 16; ++u) t += red[g & 1][u][lane];
+      v += t;
+    }
+  }
+  if (zg != 0 || idx >= lead.count) return;
+  const int n = idx / lead.row_len, k = idx - n * lead.row_len;
+  const int K = lead.bias ? lead.row_len - 1 : lead.row_len;       // the last column of a row with a bias destination is db[n]
+  if (k < K) lead.dst[(size_t)n * lead.dst_stride + k] += v;
+  else lead.bias[n] += v;
+}
+
+// The table reaches the device as kernel arguments (baked into a captured graph's node: a replay needs no host buffer to stay alive)
+constexpr int GR_CHUNK = 64;
+struct GradReduceChunk { A3dGradReduceRec rec[GR_CHUNK]; };
+__global__ __launch_bounds__(64) void grad_reduce_table_write_kernel(A3dGradReduceRec* __restrict__ table, GradReduceChunk c, int n) {
+  if ((int)threadIdx.x < n) table[threadIdx.x] = c.rec[threadIdx.x];
+}
+
 // ---------------------------------------------------------------- residual + LayerNorm
 // one wave per row, E <= 512
 __global__ __launch_bounds__(256) void add_ln_fwd_kernel(
@@ -375,14 +438,16 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(
 // the 21 312 x 60 ghost-token rows (5 MB): a chain of dependent load -> 6-step reduce -> store rounds, ~5 rows deep per wave.
 // DROP: second output dSd = dropout(dS) (the gradient through the nn.Dropout on the residual branch, dropout.hip's mask over the
 // flat index m * E + e, E % 8 == 0) -- bit-identical to a3d_dropout(dS -> dSd) afterwards, without the launch and the re-read.
-template <int LPR, bool DROP>
-__global__ __launch_bounds__(256) void add_ln_bwd_rows_kernel(
+// NW: waves per workgroup.  The chip-sized grid of the E <= 64 entries (<= 256 workgroups, ln_rows_grid) runs 16 waves per workgroup:
+// with 4 the 21 312 ghost-token rows were 888 waves, under one per SIMD, each a chain of six load -> reduce -> store rounds (10.7 us).
+template <int LPR, bool DROP, int NW = 4>
+__global__ __launch_bounds__(NW * 64) void add_ln_bwd_rows_kernel(
     const float* __restrict__ A, const float* __restrict__ R, const float* __restrict__ gamma,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in, const float* __restrict__ dY,
     float* __restrict__ dS, float* __restrict__ dgamma, float* __restrict__ dbeta, int M, int E, int rows_per_wg,
     float* __restrict__ dSd, const unsigned long long* __restrict__ drop_state, uint32_t drop_site, uint32_t drop_thr16,
-    float drop_scale) {
-  constexpr int RPW = 64 / LPR, SLOTS = 256 / LPR;
+    float drop_scale, float* __restrict__ partials) {
+  constexpr int RPW = 64 / LPR, SLOTS = NW * 64 / LPR;
   __shared__ float red_g[SLOTS][LPR * 4];
   __shared__ float red_b[SLOTS][LPR * 4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -397,7 +462,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_rows_kernel(
   float pg[4] = {0.f, 0.f, 0.f, 0.f}, pb[4] = {0.f, 0.f, 0.f, 0.f};
   const int m_beg = blockIdx.x * rows_per_wg, m_end = min(M, m_beg + rows_per_wg);
   const float inv_e = 1.0f / (float)E;
-  for (int m0 = m_beg + wave * RPW; m0 < m_end; m0 += 4 * RPW) {
+  for (int m0 = m_beg + wave * RPW; m0 < m_end; m0 += NW * RPW) {
     const int m = m0 + sub;
     const bool ok = act && m < m_end;
     float4 x = make_float4(0.f, 0.f, 0.f, 0.f), dy = x;
@@ -440,16 +505,21 @@ __global__ __launch_bounds__(256) void add_ln_bwd_rows_kernel(
       }
     }
   }
-  if (dgamma) {
+  if (dgamma || partials) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) { red_g[wave * RPW + sub][e0 + j] = pg[j]; red_b[wave * RPW + sub][e0 + j] = pb[j]; }
     __syncthreads();
-    for (int e = t; e < E; e += 256) {
+    for (int e = t; e < E; e += NW * 64) {
       float sg = 0.f, sb = 0.f;
 #pragma unroll
       for (int u = 0; u < SLOTS; ++u) { sg += red_g[u][e]; sb += red_b[u][e]; }
-      atomicAdd(&dgamma[e], sg);
-      atomicAdd(&dbeta[e], sb);
+      if (partials) {                                              // record [workgroup][2][E]: plain stores, summed in order later
+        partials[((size_t)blockIdx.x * 2 + 0) * E + e] = sg;
+        partials[((size_t)blockIdx.x * 2 + 1) * E + e] = sb;
+      } else {
+        atomicAdd(&dgamma[e], sg);
+        atomicAdd(&dbeta[e], sb);
+      }
     }
   }
 }
@@ -595,6 +665,83 @@ extern "C" int a3d_sq_wgrad_reduce(const float* partial, int nsplit, float* dW, 
   return check_launch("a3d_sq_wgrad_reduce");
 }
 
+// First stage alone (the reduction is deferred to a3d_grad_reduce_table): the plan and the partial layout of a3d_linear_wgrad_ws
+extern "C" int a3d_linear_wgrad_partials(const float* dY, int lddy, const float* X, int ldx, int has_bias, int M, int N, int K,
+                                         float* ws, size_t ws_bytes, int* nsplit_out, void* stream) {
+  if (!dY || !X || !ws || !nsplit_out || M <= 0 || N <= 0 || K <= 0) {
+    set_error("a3d_linear_wgrad_partials: bad argument (M=%d N=%d K=%d)", M, N, K);
+    return A3D_ERR_ARG;
+  }
+  const int KE = has_bias ? K + 1 : K;
+  int nsplit, rows;
+  bool two_stage;
+  wgrad_plan(M, N, KE, true, &nsplit, &rows, &two_stage);
+  if (!two_stage) {
+    set_error("a3d_linear_wgrad_partials: M=%d runs the one-stage kernel (a3d_linear_wgrad_ws_bytes is 0): nothing to defer", M);
+    return A3D_ERR_ARG;
+  }
+  if (ws_bytes < (size_t)nsplit * N * KE * sizeof(float)) {
+    set_error("a3d_linear_wgrad_partials: workspace too small (%zu bytes, need %zu)", ws_bytes, (size_t)nsplit * N * KE * sizeof(float));
+    return A3D_ERR_ARG;
+  }
+  *nsplit_out = nsplit;
+  if (linear_wgrad_split_applicable(dY, lddy, X, ldx, M))
+    return linear_wgrad_split_launch(dY, lddy, X, ldx, has_bias, M, N, K, nsplit, rows, ws, (hipStream_t)stream);
+  // db only selects the ones column here: with a partial buffer the kernel stores nothing through dW / db
+  hipLaunchKernelGGL(linear_wgrad_kernel, dim3(cdiv(N, 64), cdiv(KE, 64), nsplit), dim3(256), 0, (hipStream_t)stream, dY, lddy, X, ldx,
+                     (float*)nullptr, 0, has_bias ? ws : (float*)nullptr, M, N, K, rows, ws);
+  return check_launch("a3d_linear_wgrad_partials");
+}
+
+extern "C" int a3d_grad_reduce_table_plan(const A3dGradReduceRec* t, int nrec, int* nwg_out) {
+  if (!t || !nwg_out || nrec <= 0) { set_error("a3d_grad_reduce_table_plan: bad argument (nrec=%d)", nrec); return A3D_ERR_ARG; }
+  long long nwg = 0;
+  for (int r = 0; r < nrec;) {
+    const A3dGradReduceRec& l = t[r];
+    const int K = l.bias ? l.row_len - 1 : l.row_len;
+    if (l.group_len < 1 || r + l.group_len > nrec || !l.dst || l.count < 1 || l.row_len < 1 || K < 0 || l.dst_stride < K) {
+      set_error("a3d_grad_reduce_table_plan: record %d is no valid group leader (group_len=%d count=%d row_len=%d dst_stride=%d)", r,
+                l.group_len, l.count, l.row_len, l.dst_stride);
+      return A3D_ERR_ARG;
+    }
+    for (int g = 0; g < l.group_len; ++g) {
+      const A3dGradReduceRec& m = t[r + g];
+      if (!m.partial || m.nsplit < 1 || m.slab_stride < m.count || m.count != l.count || m.row_len != l.row_len || m.dst != l.dst ||
+          m.bias != l.bias || m.dst_stride != l.dst_stride || (g > 0 && m.group_len != 0)) {
+        set_error("a3d_grad_reduce_table_plan: record %d does not match its group leader %d (nsplit=%d slab_stride=%d count=%d)", r + g, r,
+                  m.nsplit, m.slab_stride, m.count);
+        return A3D_ERR_ARG;
+      }
+    }
+    nwg += cdiv(l.count, 64);
+    r += l.group_len;
+  }
+  if (nwg > 0x7fffffffLL) { set_error("a3d_grad_reduce_table_plan: too many outputs"); return A3D_ERR_ARG; }
+  *nwg_out = (int)nwg;
+  return A3D_OK;
+}
+
+extern "C" int a3d_grad_reduce_table_upload(A3dGradReduceRec* dev_table, const A3dGradReduceRec* host_table, int nrec, void* stream) {
+  int nwg;
+  if (!dev_table) { set_error("a3d_grad_reduce_table_upload: no device table"); return A3D_ERR_ARG; }
+  int rc = a3d_grad_reduce_table_plan(host_table, nrec, &nwg);
+  if (rc) return rc;
+  for (int r0 = 0; r0 < nrec; r0 += GR_CHUNK) {
+    GradReduceChunk c;
+    const int n = min(GR_CHUNK, nrec - r0);
+    memset(&c, 0, sizeof(c));
+    memcpy(c.rec, host_table + r0, (size_t)n * sizeof(A3dGradReduceRec));
+    hipLaunchKernelGGL(grad_reduce_table_write_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dev_table + r0, c, n);
+  }
+  return check_launch("a3d_grad_reduce_table_upload");
+}
+
+extern "C" int a3d_grad_reduce_table(const A3dGradReduceRec* dev_table, int nrec, int nwg, void* stream) {
+  if (!dev_table || nrec <= 0 || nwg <= 0) { set_error("a3d_grad_reduce_table: bad argument (nrec=%d nwg=%d)", nrec, nwg); return A3D_ERR_ARG; }
+  hipLaunchKernelGGL(grad_reduce_table_kernel, dim3(nwg), dim3(1024), 0, (hipStream_t)stream, dev_table, nrec);
+  return check_launch("a3d_grad_reduce_table");
+}
+
 extern "C" int a3d_linear_wgrad(const float* dY, int lddy, const float* X, int ldx, float* dW, int lddw,
                                 float* db, int M, int N, int K, void* stream) {
   return a3d_linear_wgrad_ws(dY, lddy, X, ldx, dW, lddw, db, M, N, K, nullptr, 0, stream);
@@ -614,6 +761,35 @@ extern "C" int a3d_add_layernorm_fwd(const float* A, const float* R, const float
   return check_launch("a3d_add_layernorm_fwd");
 }
 
+// E <= 64 rows layout: 16 waves x 4 rows = 64 rows per workgroup and pass; at most 256 workgroups, each a contiguous block of whole passes
+constexpr int LN_NW = 16;
+static int ln_rows_grid(int M, int* rows_per_wg) {
+  const int rpw = cdiv(cdiv(M, 256), 4 * LN_NW) * 4 * LN_NW;
+  *rows_per_wg = rpw;
+  return cdiv(M, rpw);
+}
+
+extern "C" int a3d_add_layernorm_bwd_partials_count(int M, int E) {
+  if (M <= 0 || E <= 0 || E > 64 || (E & 3)) return 0;
+  int rpw;
+  return ln_rows_grid(M, &rpw);
+}
+
+extern "C" int a3d_add_layernorm_bwd_partials(const float* A, const float* R, const float* gamma, const float* mean, const float* rstd,
+                                              const float* dY, float* dS, float* partials, int M, int E, void* stream) {
+  if (!A || !gamma || !mean || !rstd || !dY || !dS || !partials || a3d_add_layernorm_bwd_partials_count(M, E) <= 0 ||
+      ((((uintptr_t)A) | ((uintptr_t)R) | ((uintptr_t)dY) | ((uintptr_t)dS)) & 15) != 0) {
+    set_error("a3d_add_layernorm_bwd_partials: bad argument (M=%d E=%d; E <= 64, E %% 4 == 0, 16-byte aligned rows)", M, E);
+    return A3D_ERR_ARG;
+  }
+  int rpw;
+  const int grid = ln_rows_grid(M, &rpw);
+  hipLaunchKernelGGL((add_ln_bwd_rows_kernel<16, false, LN_NW>), dim3(grid), dim3(LN_NW * 64), 0, (hipStream_t)stream, A, R, gamma, mean,
+                     rstd, dY, dS, (float*)nullptr, (float*)nullptr, M, E, rpw, (float*)nullptr, (const unsigned long long*)nullptr, 0u,
+                     0u, 0.f, partials);
+  return check_launch("a3d_add_layernorm_bwd_partials");
+}
+
 extern "C" int a3d_add_layernorm_bwd(const float* A, const float* R, const float* gamma, const float* mean,
                                      const float* rstd, const float* dY, float* dS, float* dgamma,
                                      float* dbeta, int M, int E, void* stream) {
@@ -622,20 +798,26 @@ extern "C" int a3d_add_layernorm_bwd(const float* A, const float* R, const float
     return A3D_ERR_ARG;
   }
   if (M == 0) return A3D_OK;
-  // Measured (round 5, gpurun r05a): E = 120 22.1 -> 14.8 us per call (the trajectory model), E = 60 33.0 -> 35.1 us (Act3D's
-  // 21 312 ghost rows: no gain) -- the rows kernel serves 64 < E <= 128 only.
+  // E <= 64: the rows kernel on a chip-sized grid (ln_rows_grid), a contiguous block of rows per workgroup.  This entry has no
+  // workspace, so its <= 256 workgroups still finish with 2 E atomics each (a3d_add_layernorm_bwd_partials leaves records instead).
+  if (a3d_add_layernorm_bwd_partials_count(M, E) > 0 &&
+      ((((uintptr_t)A) | ((uintptr_t)R) | ((uintptr_t)dY) | ((uintptr_t)dS)) & 15) == 0) {
+    int rpw;
+    const int grid = ln_rows_grid(M, &rpw);
+    hipLaunchKernelGGL((add_ln_bwd_rows_kernel<16, false, LN_NW>), dim3(grid), dim3(LN_NW * 64), 0, (hipStream_t)stream, A, R, gamma, mean,
+                       rstd, dY, dS, dgamma, dbeta, M, E, rpw, (float*)nullptr, (const unsigned long long*)nullptr, 0u, 0u, 0.f,
+                       (float*)nullptr);
+    return check_launch("a3d_add_layernorm_bwd");
+  }
+  // Measured (round 5): E = 120 22.1 -> 14.8 us per call (the trajectory model) with one pass of rows per workgroup; at E = 60 that
+  // grid (1332 workgroups, 160 k same-address atomics for Act3D's 21 312 ghost rows) gave 35.1 against 33.0 us -- hence the branch above.
   if (E > 64 && E <= 128 && (E & 3) == 0 && ((((uintptr_t)A) | ((uintptr_t)R) | ((uintptr_t)dY) | ((uintptr_t)dS)) & 15) == 0) {
-    // rows-per-workgroup: one pass (16 / 8 rows) while that still fills the chip, more rows per workgroup (fewer atomics) beyond
-    const int per_pass = E <= 64 ? 16 : 8;
-    int rpw = per_pass;
-    while (cdiv(M, rpw) > 2048 && rpw < 16 * per_pass) rpw *= 2;
+    // rows-per-workgroup: one pass (8 rows) while that still fills the chip, more rows per workgroup (fewer atomics) beyond
+    int rpw = 8;
+    while (cdiv(M, rpw) > 2048 && rpw < 128) rpw *= 2;
     const int grid = cdiv(M, rpw);
-    if (E <= 64)
-      hipLaunchKernelGGL((add_ln_bwd_rows_kernel<16, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, A, R, gamma, mean, rstd, dY, dS,
-                         dgamma, dbeta, M, E, rpw, (float*)nullptr, (const unsigned long long*)nullptr, 0u, 0u, 0.f);
-    else
-      hipLaunchKernelGGL((add_ln_bwd_rows_kernel<32, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, A, R, gamma, mean, rstd, dY, dS,
-                         dgamma, dbeta, M, E, rpw, (float*)nullptr, (const unsigned long long*)nullptr, 0u, 0u, 0.f);
+    hipLaunchKernelGGL((add_ln_bwd_rows_kernel<32, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, A, R, gamma, mean, rstd, dY, dS,
+                       dgamma, dbeta, M, E, rpw, (float*)nullptr, (const unsigned long long*)nullptr, 0u, 0u, 0.f, (float*)nullptr);
     return check_launch("a3d_add_layernorm_bwd");
   }
   const int grid = min(cdiv(M, 16), 1024);
@@ -664,7 +846,7 @@ extern "C" int a3d_add_layernorm_bwd_drop(const float* A, const float* R, const 
     int rpw = 8;                                                   // as a3d_add_layernorm_bwd for this width
     while (cdiv(M, rpw) > 2048 && rpw < 128) rpw *= 2;
     hipLaunchKernelGGL((add_ln_bwd_rows_kernel<32, true>), dim3(cdiv(M, rpw)), dim3(256), 0, (hipStream_t)stream, A, R, gamma, mean, rstd,
-                       dY, dS, dgamma, dbeta, M, E, rpw, dS_drop, state, (uint32_t)site, thr, scale);
+                       dY, dS, dgamma, dbeta, M, E, rpw, dS_drop, state, (uint32_t)site, thr, scale, (float*)nullptr);
     return check_launch("a3d_add_layernorm_bwd_drop");
   }
   rc = a3d_add_layernorm_bwd(A, R, gamma, mean, rstd, dY, dS, dgamma, dbeta, M, E, stream);

@@ -584,6 +584,17 @@ extern "C" int a3d_colsum_rows(const float* src, int B, int S, int k, int ld, in
   return check_launch("a3d_colsum_rows(reduce)");
 }
 
+// first stage of a3d_colsum_rows alone (the partial rows are added by a3d_grad_reduce_table)
+extern "C" int a3d_colsum_rows_partials(const float* src, int B, int S, int k, int ld, int C, float* ws, void* stream) {
+  if (!src || !ws || B <= 0 || S <= 0 || k <= 0 || k > S || C <= 0 || ld < C) {
+    set_error("a3d_colsum_rows_partials: bad argument (B=%d S=%d k=%d ld=%d C=%d; k <= S, C <= ld)", B, S, k, ld, C);
+    return A3D_ERR_ARG;
+  }
+  const int nblk = (int)(a3d_colsum_rows_ws_floats(B, k, C) / C);
+  hipLaunchKernelGGL(colsum_rows_kernel, dim3(nblk, cdiv(C, 64)), dim3(256), 0, (hipStream_t)stream, src, B, S, k, ld, C, ws);
+  return check_launch("a3d_colsum_rows_partials");
+}
+
 extern "C" int a3d_rgb_normalize_nhwc_bf16(const float* x, const float* mean, const float* stdv, void* y, size_t N, int H, int W,
                                            void* stream) {
   const size_t HW = (size_t)H * W;

@@ -321,6 +321,7 @@ def _split_backward(tokens, run_hot, on_hot_done):
     """Backward in two stages around the FPN's output tokens: the hot path runs on detached leaves, its backward fills
     every hot-path parameter gradient and the token gradients; `on_hot_done()` (the early all-reduce) is called; then the
     token gradients are pushed through the FPN (MIOpen convolution backward).  Same gradients as one backward() call."""
+    from . import ops
     from .ops import TokenMap
     uniq, leaves = {}, []
     for t in tokens:
@@ -331,6 +332,8 @@ def _split_backward(tokens, run_hot, on_hot_done):
         leaves.append(leaf if isinstance(t, TokenMap) else leaf.tokens)      # plain tensors in, plain leaves out
     loss = run_hot(leaves)
     loss.backward()
+    ops.flush_reduce_queue()                 # the hot path's deferred gradient reductions (its end-of-backward callback ran them;
+                                             # this is the boundary the early all-reduce relies on)
     if on_hot_done is not None:
         on_hot_done()
     pairs = [(t, l.tokens.grad) for t, l in uniq.values() if t.requires_grad and l.tokens.grad is not None]

@@ -38,6 +38,9 @@ DnTailParams = _struct("DnTailParams", [(n, _p) for n in (
 
 # parameter / gradient blocks of the fused query-stream layer (a3d_qs_params / a3d_qs_grads)
 QsParams = _struct("QsParams", [(n, _p) for n in ("wv", "bv", "wo", "bo", "g1", "b1", "w1", "c1", "w2", "c2", "g2", "b2")])
+# one record of the deferred gradient-reduction table (A3dGradReduceRec)
+GradReduceRec = _struct("GradReduceRec", [("partial", _p), ("dst", _p), ("bias", _p)] +
+                        [(n, _i) for n in ("nsplit", "slab_stride", "count", "row_len", "dst_stride", "group_len")])
 QsGrads = _struct("QsGrads", [(n, _p) for n in ("dwv", "dbv", "dwo", "dbo", "dg1", "db1", "dw1", "dc1", "dw2", "dc2", "dg2", "db2")])
 
 # name -> (restype, argtypes); mirrors include/act3d_hip.h one to one
@@ -50,6 +53,13 @@ SIGNATURES = {
     "a3d_linear_wgrad_ws_bytes": (_z, [_i, _i, _i, _i]),
     "a3d_add_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
     "a3d_add_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "a3d_linear_wgrad_partials": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _z, _p, _p]),
+    "a3d_add_layernorm_bwd_partials_count": (_i, [_i, _i]),
+    "a3d_add_layernorm_bwd_partials": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "a3d_colsum_rows_partials": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
+    "a3d_grad_reduce_table_plan": (_i, [_p, _i, _p]),
+    "a3d_grad_reduce_table_upload": (_i, [_p, _p, _i, _p]),
+    "a3d_grad_reduce_table": (_i, [_p, _i, _i, _p]),
     "a3d_rope_split_qk": (_i, [_p, _i, _p, _p, _f, _p, _i, _i, _i, _i, _i, _p]),
     "a3d_split_vt": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "a3d_proj_rope_split": (_i, [_p, _i, _p, _i, _p, _i, _p, _f, _p, _i, _p, _p, _f, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p]),

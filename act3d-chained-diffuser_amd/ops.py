@@ -4,6 +4,7 @@ backward launches of libact3d_hip.so.  PyTorch only provides device memory, the 
 Parameter gradients are accumulated by the wgrad kernels straight into ``param.grad`` (the flat gradient buffer
 when the model is wrapped by ``FlatParams``) instead of being returned through autograd; see DESIGN.md.
 """
+import ctypes
 import math
 import os
 
@@ -88,11 +89,120 @@ def dgrad2d(dy2d, W, mask=None, drop=None, site=0, accum_into=None):
                       ldm=K, transposed=True, drop=drop, site=site)
 
 
+# Deferred gradient reductions.  Every two-stage column sum of the backward pass (the split-M weight gradients, the LayerNorm
+# dgamma / dbeta of the ghost-token rows, the FPN output bias owed to gathered rows) used to finish with a launch of its own: 41 + 12
+# dependent, latency-bound launches per keypose step that add into buffers nobody reads before AdamW (or the all-reduce of the hot
+# segments).  With a ReduceQueue active the first stages only leave their partial slabs behind and append a record; ONE
+# a3d_grad_reduce_table launch at the end of the backward pass (an autograd-engine callback, so loss.backward() returns with complete
+# .grad tensors) adds them -- per output: the slabs of a record in a fixed order, the records of one destination (tied weights: one
+# per pyramid level) in the order they were appended, then one add into the gradient.  No atomics, the same bits on every run.
+# A3D_DEFER_REDUCE=0: no queue is ever created and every reduction is launched where it arises (the A/B switch).
+DEFER_REDUCE = os.environ.get("A3D_DEFER_REDUCE", "1") not in ("0", "", "off")
+
+
+def build_reduce_table(records):
+    """Host side of the table: records = [(partial_ptr, nsplit, slab_stride, count, row_len, dst_ptr, dst_stride, bias_ptr)] in the
+    order they were appended -> a ctypes array of lib.GradReduceRec in which the records of one destination are adjacent (groups in
+    the order of their first record, members in append order) and each group's first record carries the group's size."""
+    groups = {}
+    for r in records:
+        partial, nsplit, slab, count, row_len, dst, dst_stride, bias = r
+        key = (int(dst), int(bias or 0), int(count), int(row_len), int(dst_stride))
+        groups.setdefault(key, []).append(r)
+    table = (L.GradReduceRec * len(records))()
+    i = 0
+    for members in groups.values():
+        for j, (partial, nsplit, slab, count, row_len, dst, dst_stride, bias) in enumerate(members):
+            t = table[i]
+            t.partial, t.dst, t.bias = int(partial), int(dst), (int(bias) if bias else None)
+            t.nsplit, t.slab_stride, t.count, t.row_len, t.dst_stride = int(nsplit), int(slab), int(count), int(row_len), int(dst_stride)
+            t.group_len = len(members) if j == 0 else 0
+            i += 1
+    return table
+
+
+def reduce_table_launch(records, device, st=None):
+    """One a3d_grad_reduce_table launch over `records` (see build_reduce_table) on the current stream."""
+    if not records:
+        return
+    table = build_reduce_table(records)
+    n, nwg = len(records), ctypes.c_int(0)
+    L.call("a3d_grad_reduce_table_plan", table, n, ctypes.byref(nwg))
+    st = L.stream() if st is None else st
+    dev = torch.empty((n * ctypes.sizeof(L.GradReduceRec) // 8,), device=device, dtype=torch.int64)
+    L.call("a3d_grad_reduce_table_upload", dev.data_ptr(), table, n, st)
+    L.call("a3d_grad_reduce_table", dev.data_ptr(), n, nwg.value, st)
+
+
+class ReduceQueue:
+    """The pending second stages of one backward pass.  Records are taken only on the stream the forward pass ran on (autograd runs
+    the main path's backward nodes there, and the caller of backward() goes on there; a first stage on another stream -- the query
+    stream's side stream -- keeps its own second stage) and only while the autograd engine runs (the flush is its final callback)."""
+    current = None                                # the queue of the last forward pass (begin_grad_sinks), None: nothing is deferred
+    flushes = 0                                   # table launches so far (tests and traces look at it)
+
+    def __init__(self, stream=None, device=None):
+        self.records, self.keep = [], []
+        self.stream, self.device, self.armed = stream, device, False
+
+    def accepts(self, device):
+        """Whether a first stage enqueued now on the current stream may leave its reduction to the flush; arms the flush."""
+        if self.stream is None or torch.cuda.current_stream(device) != self.stream:
+            return False
+        if not self.armed:
+            try:
+                torch.autograd.Variable._execution_engine.queue_callback(self._callback)
+            except RuntimeError:                  # not inside a backward pass: nobody would flush
+                return False
+            if self.records:                      # left over by a pass that never reached its callback (an exception)
+                self.records, self.keep = [], []
+            self.armed = True
+        return True
+
+    def add(self, owner, partial_ptr, nsplit, slab_stride, count, row_len, dst_ptr, dst_stride, bias_ptr=None):
+        """owner: the tensor that holds the partial slabs (kept alive until the flush has been enqueued)"""
+        self.keep.append(owner)
+        self.records.append((partial_ptr, nsplit, slab_stride, count, row_len, dst_ptr, dst_stride, bias_ptr))
+
+    def flush(self):
+        if not self.records:
+            return
+        records, self.records, self.keep, keep = self.records, [], [], self.keep
+        with torch.cuda.stream(self.stream):
+            reduce_table_launch(records, self.device, self.stream.cuda_stream)
+        ReduceQueue.flushes += 1
+        del keep
+
+    def _callback(self):
+        self.armed = False
+        self.flush()
+
+
+def reduce_queue(device):
+    """The active queue if it takes a record from the current stream now, else None."""
+    q = ReduceQueue.current
+    return q if (q is not None and q.accepts(device)) else None
+
+
+def flush_reduce_queue():
+    """Enqueue the pending reductions now (the split backward calls it at its hot-path boundary; a no-op when none are pending)."""
+    if ReduceQueue.current is not None:
+        ReduceQueue.current.flush()
+
+
 def wgrad_raw(dy_ptr, lddy, x_ptr, ldx, gw_ptr, lddw, gb_ptr, M, N, K, device, st=None):
     """dW += dY^T X, db += sum dY through a3d_linear_wgrad_ws: large-M reductions run two-stage (per-split partials in
-    a workspace + ordered reduce) instead of memory-side float atomics."""
+    a workspace + ordered reduce) instead of memory-side float atomics.  With a ReduceQueue active the ordered reduce of a
+    two-stage shape is left to the queue's flush."""
     nbytes = L.load().a3d_linear_wgrad_ws_bytes(M, N, K, 0 if gb_ptr is None else 1)
     ws = torch.empty((nbytes // 4,), device=device, dtype=F32) if nbytes else None
+    q = reduce_queue(device) if (nbytes and (st is None or st == L.stream())) else None
+    if q is not None:
+        ns, KE = ctypes.c_int(0), K + (0 if gb_ptr is None else 1)
+        L.call("a3d_linear_wgrad_partials", dy_ptr, lddy, x_ptr, ldx, 0 if gb_ptr is None else 1, M, N, K, ws.data_ptr(), nbytes,
+               ctypes.byref(ns), L.stream())
+        q.add(ws, ws.data_ptr(), ns.value, N * KE, N * KE, KE, gw_ptr, lddw, gb_ptr)
+        return
     L.call("a3d_linear_wgrad_ws", dy_ptr, lddy, x_ptr, ldx, gw_ptr, lddw, gb_ptr, M, N, K,
            None if ws is None else ws.data_ptr(), nbytes, st if st is not None else L.stream())
 
@@ -123,6 +233,24 @@ def add_layernorm_bwd(a2d, r2d, g, b, mean, rstd, dy2d, drop=None, site=0):
     M, E = a2d.shape
     ds = torch.empty_like(a2d)
     gg, gb = grad_buf(g), grad_buf(b)
+    cnt = L.load().a3d_add_layernorm_bwd_partials_count(M, E) if DEFER_REDUCE else 0
+    if cnt > 0 and ((a2d.data_ptr() | (0 if r2d is None else r2d.data_ptr()) | dy2d.data_ptr() | ds.data_ptr()) & 15) == 0:
+        # E <= 64: per-workgroup (sum dy * xhat, sum dy) records instead of same-address atomics, added in a fixed order by the
+        # queue's flush (or right here when nothing is deferred)
+        part = torch.empty((cnt, 2, E), device=a2d.device, dtype=F32)
+        L.call("a3d_add_layernorm_bwd_partials", a2d.data_ptr(), None if r2d is None else r2d.data_ptr(), g.data_ptr(),
+               mean.data_ptr(), rstd.data_ptr(), dy2d.data_ptr(), ds.data_ptr(), part.data_ptr(), M, E, L.stream())
+        recs = [(part.data_ptr(), cnt, 2 * E, E, E, gg.data_ptr(), E, None),
+                (part.data_ptr() + 4 * E, cnt, 2 * E, E, E, gb.data_ptr(), E, None)]
+        q = reduce_queue(a2d.device)
+        if q is not None:
+            for r in recs:
+                q.add(part, *r)
+        else:
+            reduce_table_launch(recs, a2d.device)
+        if drop is not None:
+            return ds, dropout_raw(ds, drop, site)
+        return ds
     if drop is not None and DROP_FOLD:
         dsd = torch.empty_like(a2d)
         L.call("a3d_add_layernorm_bwd_drop", a2d.data_ptr(), None if r2d is None else r2d.data_ptr(), g.data_ptr(),
@@ -568,6 +696,18 @@ class GradSink:
         linear_raw(self.dkv.data_ptr(), ld, wstack.data_ptr(), E, None, M, E, K, self.device, act=3 if acc else 0, transposed=True,
                    out=self.buf.view(M, E))
         # [dW_0; dW_1; ...] = [dKV_0 | dKV_1 | ...]^T X, the bias gradients alongside
+        nbytes = L.load().a3d_linear_wgrad_ws_bytes(M, K, E, 1)
+        q = reduce_queue(self.device) if nbytes else None
+        if q is not None:
+            # first stage once over the stacked rows; every block's slice of the partial tiles goes straight to its own gradient
+            ws = torch.empty((nbytes // 4,), device=self.device, dtype=F32)
+            ns, KE = ctypes.c_int(0), E + 1
+            L.call("a3d_linear_wgrad_partials", self.dkv.data_ptr(), ld, self.x.data_ptr(), E, 1, M, K, E, ws.data_ptr(), nbytes,
+                   ctypes.byref(ns), L.stream())
+            for i, (_, gw, gb) in enumerate(self.parked):
+                q.add(ws, ws.data_ptr() + 4 * i * E2 * KE, ns.value, K * KE, E2 * KE, KE, gw.data_ptr(), gw.stride(0), gb.data_ptr())
+            self.dkv, self.parked, self.x = None, [], None
+            return
         gstack = torch.zeros((K, E), device=self.device, dtype=F32)
         gbstack = torch.zeros((K,), device=self.device, dtype=F32)
         wgrad_raw(self.dkv.data_ptr(), ld, self.x.data_ptr(), E, gstack.data_ptr(), E, gbstack.data_ptr(), M, K, E, self.device)
@@ -635,6 +775,9 @@ def begin_grad_sinks():
         sk.buf, sk.event, sk.writers = None, None, 0
         sk.dkv, sk.parked, sk.x = None, [], None
     GradSink.live = []
+    ReduceQueue.current = None
+    if DEFER_REDUCE and torch.cuda.is_available():
+        ReduceQueue.current = ReduceQueue(torch.cuda.current_stream(), torch.device("cuda", torch.cuda.current_device()))
 
 
 def attach_grad_sink(t, registry=None):
@@ -1315,7 +1458,12 @@ class BuildContextFn(torch.autograd.Function):
         if ctx.bias is not None and ctx.bias.requires_grad:
             ws = torch.empty((L.load().a3d_colsum_rows_ws_floats(B, k, E),), device=dctx.device, dtype=F32)
             gb = grad_buf(ctx.bias)
-            L.call("a3d_colsum_rows", dctx.data_ptr(), B, k + X, k, E, E, gb.data_ptr(), E, ws.data_ptr(), L.stream())
+            q = reduce_queue(dctx.device)
+            if q is not None:
+                L.call("a3d_colsum_rows_partials", dctx.data_ptr(), B, k + X, k, E, E, ws.data_ptr(), L.stream())
+                q.add(ws, ws.data_ptr(), ws.numel() // E, E, E, E, gb.data_ptr(), E, None)
+            else:
+                L.call("a3d_colsum_rows", dctx.data_ptr(), B, k + X, k, E, E, gb.data_ptr(), E, ws.data_ptr(), L.stream())
         cc = ctx.conv_ctx
         if (cc is not None and not cc.dense and idx is not None and SPARSE_FPN_WGRAD and cc.x is not None and cc.x.shape[1] == 64
                 and cc.ncam * cc.x.shape[2] * cc.x.shape[3] == Npts and E <= 64):

@@ -58,9 +58,47 @@ int a3d_linear_wgrad_ws(const float* dY, int lddy, const float* X, int ldx, floa
  * Replaces `output = self.norm(query + dropout(attn_output))` layers.py:308-309, 329-331, 158-159. */
 int a3d_add_layernorm_fwd(const float* A, const float* R, const float* gamma, const float* beta, float* Y,
                           float* mean, float* rstd, int M, int E, float eps, void* stream);
-/* dS = d(A+R); dgamma/dbeta accumulate atomically (both NULL to skip). */
+/* dS = d(A+R); dgamma/dbeta accumulate atomically (both NULL to skip).  E <= 64 (E % 4 == 0, 16-byte aligned rows): the rows
+ * kernel of a3d_add_layernorm_bwd_partials on its chip-sized grid, at most 256 workgroups x 2 E atomics (this entry has no
+ * workspace for records; the hot path goes through a3d_add_layernorm_bwd_partials + a3d_grad_reduce_table). */
 int a3d_add_layernorm_bwd(const float* A, const float* R, const float* gamma, const float* mean, const float* rstd,
                           const float* dY, float* dS, float* dgamma, float* dbeta, int M, int E, void* stream);
+
+/* ---- deferred gradient reductions -------------------------------------------------------------------------
+ * First stages that only leave partial column sums behind, and ONE table-driven launch that finishes every
+ * reduction of a backward pass in a fixed order (no atomics: the same bits on every run). */
+/* First stage of a3d_linear_wgrad_ws alone: the same plan and the same partial layout ws[nsplit][N][KE] (KE = K + 1 with
+ * has_bias: column K holds the bias gradient), nothing is written to dW.  *nsplit_out (host) receives the slab count.
+ * Serves the shapes for which a3d_linear_wgrad_ws_bytes is non-zero; any other shape is A3D_ERR_ARG. */
+int a3d_linear_wgrad_partials(const float* dY, int lddy, const float* X, int ldx, int has_bias, int M, int N, int K,
+                              float* ws, size_t ws_bytes, int* nsplit_out, void* stream);
+/* LayerNorm backward for E <= 64, E % 4 == 0 and 16-byte aligned A / R / dY / dS: dS as a3d_add_layernorm_bwd, the column
+ * sums as records partials[count][2][E] (row 0: sum dy * xhat -> dgamma, row 1: sum dy -> dbeta), one per workgroup, each
+ * workgroup walking a contiguous block of rows.  a3d_add_layernorm_bwd_partials_count is the host-side query: the record
+ * count for (M, E), 0 when the shape is not served. */
+int a3d_add_layernorm_bwd_partials_count(int M, int E);
+int a3d_add_layernorm_bwd_partials(const float* A, const float* R, const float* gamma, const float* mean, const float* rstd,
+                                   const float* dY, float* dS, float* partials, int M, int E, void* stream);
+/* First stage of a3d_colsum_rows alone: ws[a3d_colsum_rows_ws_floats(B, k, C) / C][C]. */
+int a3d_colsum_rows_partials(const float* src, int B, int S, int k, int ld, int C, float* ws, void* stream);
+/* One record of the reduction table.  Output i < count of a record is sum_z partial[z * slab_stride + i]; with n = i / row_len
+ * and c = i % row_len it is added to dst[n * dst_stride + c], or -- bias != NULL and c == row_len - 1 -- to bias[n].  Records
+ * that add into the same destination are adjacent: the first (the leader) carries their number in group_len, the others 0;
+ * they share count, row_len, dst, dst_stride and bias, and their sums are added in table order, then to the destination once. */
+typedef struct {
+  const float* partial;
+  float* dst;
+  float* bias;
+  int nsplit, slab_stride, count, row_len, dst_stride, group_len;
+} A3dGradReduceRec;
+/* Host-side: checks a table (A3D_ERR_ARG with a message on a malformed record) and returns the workgroup count of its
+ * launch through *nwg_out. */
+int a3d_grad_reduce_table_plan(const A3dGradReduceRec* host_table, int nrec, int* nwg_out);
+/* Copies a host table into device memory (nrec records) as kernel arguments of small writer launches on `stream`: nothing
+ * on the host has to outlive the call, also under graph capture. */
+int a3d_grad_reduce_table_upload(A3dGradReduceRec* dev_table, const A3dGradReduceRec* host_table, int nrec, void* stream);
+/* The reduction: one launch of nwg workgroups (from a3d_grad_reduce_table_plan) over the device table. */
+int a3d_grad_reduce_table(const A3dGradReduceRec* dev_table, int nrec, int nwg, void* stream);
 
 /* ---- RoPE-3D + operand formatting ---------------------------------------------------------------------- */
 /* dst(QK format) = split_bf16(rope3d(Y[:, :E] * scale, xyz)); xyz NULL = no rotation.  freq: E/6 device floats
