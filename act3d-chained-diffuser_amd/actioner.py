@@ -18,10 +18,11 @@ import random
 
 import torch
 
-from .diffusion import RANK_MAX_CANDIDATES, check_scene, check_clearance_args, check_num_samples, check_rot_weight, check_scene_select
+from .diffusion import RANK_MAX_CANDIDATES, check_scene, check_clearance_args, check_num_samples, check_rot_weight, check_scene_select, \
+    check_guide, check_guide_shape
 
 _TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight",
-            "scene_mask", "clear_margin", "clear_skip")
+            "scene_mask", "clear_margin", "clear_skip", "guide")
 
 
 def _same_tensors(a, b):
@@ -246,8 +247,8 @@ class Actioner:
         (B, history, >= action_dim), read only with predict_keypose=False; trajectory_mask (B, L), needed with
         predict_trajectory=True.  Returns {"action": (B, 8) or gt_action[:, -1], "trajectory": compute_trajectory's result or None,
         "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps, select,
-        rot_weight, scene_mask, clear_margin, clear_skip) go to compute_trajectory unchanged (a rule that weighs "clearance" scores the
-        candidates against pcds[:, -1]); with select the candidates are ranked on the device, "trajectory" is the
+        rot_weight, scene_mask, clear_margin, clear_skip, guide) go to compute_trajectory unchanged (a rule that weighs "clearance"
+        scores the candidates against pcds[:, -1], and `guide` steers the waypoints off that cloud while they are drawn); with select the candidates are ranked on the device, "trajectory" is the
         selected one (B, L, 8) and self.last_ranking mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
         and the sampling loop as graphs."""
         bad = [k for k in sample_kw if k not in _TRAJ_KW]
@@ -269,6 +270,19 @@ class Actioner:
                     raise ValueError("pcds must be (B, history, cameras, 3, H, W)")
                 check_scene(pcds[:, -1], sample_kw.get("scene_mask"), pcds.shape[0])
                 check_clearance_args(sample_kw.get("clear_margin", 0.05), sample_kw.get("clear_skip", (1, 1)))
+        if sample_kw.get("guide") is not None:
+            # the guide step's own argument errors, before the keypose half launches anything
+            if not self._predict_trajectory:
+                raise ValueError("guide steers sampled trajectories: it needs predict_trajectory=True")
+            check_guide(sample_kw["guide"])
+            if not torch.is_tensor(pcds) or pcds.dim() != 6:
+                raise ValueError("pcds must be (B, history, cameras, 3, H, W)")
+            if not torch.is_tensor(trajectory_mask) or trajectory_mask.dim() != 2:
+                raise ValueError("guide needs trajectory_mask (B, L)")
+            G = sample_kw.get("num_samples")
+            check_guide_shape(1 if G is None else check_num_samples(G), trajectory_mask.shape[1], self._action_dim + 2)
+            check_scene(pcds[:, -1], sample_kw.get("scene_mask"), pcds.shape[0])
+            check_clearance_args(sample_kw.get("clear_margin", 0.05), sample_kw.get("clear_skip", (1, 1)))
         self._check(rgbs, pcds, gripper, gt_action, trajectory_mask, use_graph, ghost_points)
         share = self._sharing()
         output = {"action": None, "attention": {}}

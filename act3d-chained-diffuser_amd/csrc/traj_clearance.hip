@@ -17,25 +17,10 @@
 // d^2 of a pair is fmaf(dz, dz, fmaf(dy, dy, dx * dx)) of the three differences, written out, with contraction off around it: one
 // expression, the same bits wherever it is inlined.  The minimum of a set of floats is exact and does not depend on the order, so
 // `nearest` does not depend on the chunking, the tile split or the run.  No atomics.
-#include "a3d_common.h"
+#include "traj_points.h"
 #include "../../include/act3d_hip.h"
-#include <float.h>
 
 namespace a3d {
-
-constexpr int TC_THREADS = 256;
-constexpr int TC_TILE = 512;            // points staged per pass: 8 KB of LDS
-constexpr int TC_MAX_G = 64;
-constexpr int TC_TARGET_BLOCKS = 512;   // what the entry aims for when it chooses the chunk count (two workgroups per CU)
-constexpr int TC_MAX_CHUNKS = 4096;
-
-__device__ __forceinline__ bool tc_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
-__device__ __forceinline__ float tc_dist2(float px, float py, float pz, const f32x4 s) {
-#pragma clang fp contract(off)
-  const float dx = px - s[0], dy = py - s[1], dz = pz - s[2];
-  return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
 
 struct TrajClearArgs {
   const float* poses;              // [B][G][L][Dp]
@@ -87,18 +72,7 @@ __global__ __launch_bounds__(TC_THREADS) void traj_clear_partial(const TrajClear
   for (long long base = first; base < last; base += TC_TILE) {
     const int cnt = (int)min((long long)TC_TILE, last - base);
     __syncthreads();                               // the previous pass has read pts
-    for (int j = tid; j < TC_TILE; j += TC_THREADS) {
-      f32x4 v = {INFINITY, 0.f, 0.f, 0.f};
-      if (j < cnt) {
-        const long long n = base + j;
-        const long long c = n / a.n_pix, p = n - c * a.n_pix;
-        const float* s = S + (size_t)c * 3 * a.n_pix + p;
-        const float x = s[0], y = s[a.n_pix], z = s[2 * (size_t)a.n_pix];
-        const bool ok = tc_finite(x) && tc_finite(y) && tc_finite(z) && !(M && M[n]);
-        if (ok) { v[0] = x; v[1] = y; v[2] = z; }
-      }
-      pts[j] = v;                                  // slots past cnt hold dropped points: the loop below needs no tail
-    }
+    tc_stage_points(pts, S, M, base, cnt, a.n_pix, tid);
     __syncthreads();
     const int cnt_up = (cnt + 3) & ~3;             // whole groups of 4 points; TC_TILE is a multiple of 4 npg for npg <= 4
     for (int j = pg * 4; j < cnt_up; j += 4 * npg) {
@@ -195,27 +169,6 @@ __global__ __launch_bounds__(TC_THREADS) void traj_clear_final(const TrajClearAr
     nbad += __shfl_xor(nbad, o, 64);
   }
   if (act && sub == 0) a.clearance[(size_t)b * G + g] = nbad > 0 ? NAN : (ns > 0 ? sum / (float)ns : 0.f);
-}
-
-// row slots per lane and row groups per workgroup for R rows per scene
-static void tc_shape(long long R, int* rpt, int* nrg, int* row_tiles) {
-  *rpt = R <= 256 ? 1 : (R <= 512 ? 2 : 4);
-  const long long per_tile = (long long)TC_THREADS * *rpt;
-  *row_tiles = (int)((R + per_tile - 1) / per_tile);
-  const long long groups = (R + 64LL * *rpt - 1) / (64LL * *rpt);     // waves' worth of rows, one tile when <= 4
-  *nrg = groups >= 3 ? 4 : (int)groups;
-}
-
-static int tc_chunks(int B, int G, int L, long long N, int n_chunks) {
-  if (n_chunks > 0) return n_chunks;
-  int rpt, nrg, row_tiles;
-  tc_shape((long long)G * L, &rpt, &nrg, &row_tiles);
-  const long long per = (long long)B * row_tiles;
-  long long c = (TC_TARGET_BLOCKS + per - 1) / per;
-  const long long by_points = (N + TC_TILE - 1) / TC_TILE;            // a chunk is at least one staged tile
-  if (c > by_points) c = by_points;
-  if (c > TC_MAX_CHUNKS) c = TC_MAX_CHUNKS;
-  return (int)(c < 1 ? 1 : c);
 }
 
 }  // namespace a3d

@@ -18,7 +18,8 @@ draws; `visual_tokens` bypasses the backbone + FPN; `num_inference_steps` / `sch
 schedule; `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8);
 `fused_conditioning=True` builds the sampler's conditioning tensors in one launch (a3d_traj_condition); `select` / `rot_weight`
 rank the candidates on the device and return the selected trajectory (rank_trajectories, a3d_traj_rank), optionally against the
-observed point cloud (trajectory_clearance, a3d_traj_clearance: the "clearance" term of a select rule).
+observed point cloud (trajectory_clearance, a3d_traj_clearance: the "clearance" term of a select rule); `guide` steers the waypoints
+off that cloud while they are drawn (guide_trajectories, a3d_traj_guide, between sampler steps).
 Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
 attention weights, residual branches, FFN -- and in the traj_encoder / regressor MLPs: layers.py:10,
 diffusion_head.py:46,183,193) runs on a device-resident Philox stream (csrc/dropout.hip, attention kernels): same
@@ -374,8 +375,7 @@ def trajectory_clearance(trajectories, trajectory_mask, scene, scene_mask=None, 
     O.L.require_gpu(trajectories, trajectory_mask, scene, scene_mask)
     P = O._c(trajectories.detach().float())
     tm = _mask_bytes(trajectory_mask)
-    S = scene.detach().float()
-    S = O._c(S) if S.dim() == 5 else S.transpose(1, 2).contiguous()       # (B, N, 3) -> (B, 3, N) = (B, 1, 3, N): the one copy
+    S = _scene_planar(scene)                                              # (B, N, 3) -> (B, 3, N) = (B, 1, 3, N): the one copy
     sm = None if scene_mask is None else _mask_bytes(scene_mask)
     dev = P.device
     nearest = torch.empty((B, G, Ln), device=dev, dtype=torch.float32)
@@ -384,6 +384,130 @@ def trajectory_clearance(trajectories, trajectory_mask, scene, scene_mask=None, 
     O.L.call("a3d_traj_clearance", P.data_ptr(), tm.data_ptr(), S.data_ptr(), None if sm is None else sm.data_ptr(), n_cam, n_pix, mg,
              sh, st, nearest.data_ptr(), clearance.data_ptr(), ws.data_ptr(), 0, B, G, Ln, Dp, O.L.stream())
     return TrajectoryClearance(nearest, clearance)
+
+
+# ------------------------------------------------------------------------------------------------ clearance guidance
+GUIDE_MAX_ROWS = 256                    # a3d_traj_guide: one thread per row of a trajectory
+GUIDE_KEYS = ("push", "smooth", "start")
+Guidance = collections.namedtuple("Guidance", ("steps", "nearest"))
+
+
+def check_guide_args(push, smooth):
+    """-> (push, smooth) of a guide step as floats, or ValueError: both in [0, 1], not both 0"""
+    for name, v in (("push", push), ("smooth", smooth)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0 or v > 1:
+            raise ValueError("%s must be a number in [0, 1], got %r" % (name, v))
+    if push == 0 and smooth == 0:
+        raise ValueError("push and smooth are both 0: the guide step would do nothing")
+    return float(push), float(smooth)
+
+
+def check_guide(guide):
+    """compute_trajectory's `guide` -> None, or (push, smooth, start): a number is the push; a dict maps a subset of "push" (default
+    1.0), "smooth" (0.0) and "start" (0.5, in [0, 1)) to numbers, unknown keys raise"""
+    if guide is None:
+        return None
+    if isinstance(guide, dict):
+        bad = [k for k in guide if k not in GUIDE_KEYS]
+        if bad:
+            raise ValueError("guide has unknown keys %s; the keys are %s" % (bad, list(GUIDE_KEYS)))
+        push, smooth, start = guide.get("push", 1.0), guide.get("smooth", 0.0), guide.get("start", 0.5)
+    elif isinstance(guide, (int, float)) and not isinstance(guide, bool):
+        push, smooth, start = guide, 0.0, 0.5
+    else:
+        raise ValueError("guide must be None, a number (the push) or a dict over %s, got %r" % (list(GUIDE_KEYS), guide))
+    push, smooth = check_guide_args(push, smooth)
+    if isinstance(start, bool) or not isinstance(start, (int, float)) or not math.isfinite(start) or start < 0 or start >= 1:
+        raise ValueError("guide['start'] must be a number in [0, 1), got %r" % (start,))
+    return push, smooth, float(start)
+
+
+def check_guide_shape(G, Ln, D):
+    """what a3d_traj_guide serves: G candidates per scene, Ln rows, D signal channels"""
+    if G > RANK_MAX_CANDIDATES:
+        raise ValueError("the guide step serves at most %d candidates per scene, got %d" % (RANK_MAX_CANDIDATES, G))
+    if Ln > GUIDE_MAX_ROWS:
+        raise ValueError("the guide step serves at most %d rows per trajectory, got L = %d" % (GUIDE_MAX_ROWS, Ln))
+    if D not in (9, 10):
+        raise ValueError("the guide step reads signal rows of 9 or 10 channels, got %d" % D)
+
+
+def guided_segments(n, start):
+    """The launch list of a sampling loop of n executed steps guided from `start` on: [(first, count, guided)] over step POSITIONS.
+    Step position i is guided iff i >= floor(start n) (so the terminal step always is; 1e-9 is added before the floor, so that a
+    start written as i / n means position i whatever its rounding).  Each maximal run of unguided steps is ONE entry (one sampler
+    launch where the path runs several steps per launch); each guided step is an entry of its own: a one-step sampler launch, then
+    the guide pair.  start None: the whole loop, unguided."""
+    n = int(n)
+    if start is None:
+        return [(0, n, False)]
+    if n < 1:
+        return []
+    g0 = min(n - 1, max(0, int(math.floor(start * n + 1e-9))))
+    return ([(0, g0, False)] if g0 > 0 else []) + [(i, 1, True) for i in range(g0, n)]
+
+
+def _guide_launch(x, tm, cm, bounds, S, sm, n_cam, n_pix, margin, sh, st, push, smooth, nearest, ws, B, G, Ln):
+    """a3d_traj_guide on prepared buffers: x (B G, L, D) contiguous fp32 signals, updated in place"""
+    O.L.call("a3d_traj_guide", x.data_ptr(), x.shape[-1], tm.data_ptr(), None if cm is None else cm.data_ptr(), bounds.data_ptr(),
+             S.data_ptr(), None if sm is None else sm.data_ptr(), n_cam, n_pix, margin, sh, st, push, smooth,
+             None if nearest is None else nearest.data_ptr(), ws.data_ptr(), 0, B, G, Ln, O.L.stream())
+
+
+def _scene_planar(scene):
+    """a checked scene as fp32 [B][C][3][n_pix], in place when it already is: (B, N, 3) rows are transposed once"""
+    S = scene.detach().float()
+    return O._c(S) if S.dim() == 5 else S.transpose(1, 2).contiguous()
+
+
+def guide_trajectories(signals, trajectory_mask, scene, bounds, *, scene_mask=None, cond_mask=None, margin=0.05, skip=(1, 1),
+                       push=1.0, smooth=0.0, want_nearest=False):
+    """One clearance-guidance step on trajectory signals, IN PLACE, in two launches (a3d_traj_guide, csrc/traj_guide.hip): every
+    free waypoint closer than `margin` to its nearest counted scene point is moved `push` of the way out to the margin sphere of that
+    point, and `smooth` of the way to the midpoint of its two neighbouring valid rows (all positions read before any update).
+    signals: (B, G, L, D) or (B, L, D) contiguous fp32, D = 9 or 10, as the sampler holds them (trace entries of compute_trajectory):
+    channels 0..2 are positions normalised to `bounds` (2, 3); nothing else is read or written.  trajectory_mask (B, L), non-zero =
+    padded row; scene / scene_mask / margin / skip: the arguments of trajectory_clearance, `scene` in world coordinates.
+    cond_mask: None or the sampler's in-painting mask, B G L D bytes (bool or uint8): a row whose first byte is set is pinned.
+    A row is free when it is valid, scored by the skip rule (skip[0] <= j < n - skip[1] over its rank j among the n valid rows), not
+    pinned and finite; every other row keeps its bits, pinned rows still anchor the smoothing of their neighbours.
+    Returns nearest (the shape of signals without D: the distance to the nearest counted point BEFORE the push, +inf on padded rows
+    and without a counted point, NaN where the row is not finite) with want_nearest, else None.  Bit-identical from run to run."""
+    if not torch.is_tensor(signals) or signals.dim() not in (3, 4):
+        raise ValueError("signals must be a (B, G, L, D) or (B, L, D) tensor, got %s" % (
+            tuple(signals.shape) if torch.is_tensor(signals) else type(signals).__name__,))
+    if signals.dtype != torch.float32 or not signals.is_contiguous():
+        raise ValueError("signals are updated in place: they must be contiguous fp32, got %s%s" % (
+            signals.dtype, "" if signals.is_contiguous() else " (not contiguous)"))
+    B, G, Ln, D = signals.shape if signals.dim() == 4 else (signals.shape[0], 1) + tuple(signals.shape[1:])
+    if min(B, G, Ln) < 1:
+        raise ValueError("signals has an empty dimension: %s" % (tuple(signals.shape),))
+    check_guide_shape(G, Ln, D)
+    if not torch.is_tensor(trajectory_mask) or tuple(trajectory_mask.shape) != (B, Ln):
+        raise ValueError("trajectory_mask must be (B, L) = %s, got %s" % (
+            (B, Ln), tuple(trajectory_mask.shape) if torch.is_tensor(trajectory_mask) else type(trajectory_mask).__name__))
+    n_cam, n_pix = check_scene(scene, scene_mask, B)
+    mg, sh, st = check_clearance_args(margin, skip)
+    push, smooth = check_guide_args(push, smooth)
+    if cond_mask is not None:
+        if not torch.is_tensor(cond_mask) or cond_mask.numel() != signals.numel() or cond_mask.shape[-1] != D:
+            raise ValueError("cond_mask must hold one byte per signal element, (B G, L, D) = %s, got %s" % (
+                (B * G, Ln, D), tuple(cond_mask.shape) if torch.is_tensor(cond_mask) else type(cond_mask).__name__))
+        if cond_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("cond_mask must be bool or uint8, got %s" % cond_mask.dtype)
+    if not torch.is_tensor(bounds):
+        bounds = torch.as_tensor(bounds, dtype=torch.float32)
+    if tuple(bounds.shape) != (2, 3):
+        raise ValueError("bounds must be (2, 3), got %s" % (tuple(bounds.shape),))
+    bounds = bounds.to(device=signals.device, dtype=torch.float32)
+    O.L.require_gpu(signals, trajectory_mask, scene, scene_mask, cond_mask)
+    dev = signals.device
+    nearest = torch.empty(signals.shape[:-1], device=dev, dtype=torch.float32) if want_nearest else None
+    ws = torch.empty((O.L.load().a3d_traj_guide_ws_floats(B, G, Ln, n_cam * n_pix, 0),), device=dev, dtype=torch.float32)
+    _guide_launch(signals, _mask_bytes(trajectory_mask), None if cond_mask is None else _mask_bytes(cond_mask), O._c(bounds),
+                  _scene_planar(scene), None if scene_mask is None else _mask_bytes(scene_mask), n_cam, n_pix, mg, sh, st, push, smooth,
+                  nearest, ws, B, G, Ln)
+    return nearest
 
 
 def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, select="consensus", rot_weight=1.0, scene=None,
@@ -1047,6 +1171,7 @@ class DiffusionPlanner(nn.Module):
         self._tables = None
         self._graph = None
         self.last_ranking = None
+        self.last_guidance = None
 
     # ---- helpers (diffusion_model.py:187-230)
     def tables(self, device):
@@ -1139,7 +1264,7 @@ class DiffusionPlanner(nn.Module):
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
                            return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None,
                            fused_conditioning=False, select=None, rot_weight=1.0, scene_mask=None, clear_margin=0.05,
-                           clear_skip=(1, 1)):
+                           clear_skip=(1, 1), guide=None):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
@@ -1162,7 +1287,16 @@ class DiffusionPlanner(nn.Module):
         A rule that weighs "clearance" (or the preset "clear") scores the candidates against THIS call's pcd_obs, the caller's
         tensor in world coordinates, read in place (trajectory_clearance); scene_mask (B, C, H, W) drops points (the robot's own),
         clear_margin / clear_skip are its margin and skip.  self.last_ranking then also carries clearance (B, G) and nearest
-        (B, G, L), before candidates."""
+        (B, G, L), before candidates.
+        guide: clearance guidance WHILE the trajectory is drawn (guide_trajectories, a3d_traj_guide).  A number is the push; a dict
+        maps "push" (default 1.0), "smooth" (0.0) and "start" (0.5, in [0, 1)) to numbers.  With n executed steps, the step at
+        position i >= floor(start n) is followed by one guide step on the signal it produced (the terminal step always is), on
+        every sampler path: guided_segments is the launch list, each run of unguided steps stays one launch where the path has
+        one.  The cloud is THIS call's pcd_obs in world coordinates, read in place when eager (a replayed graph reads a copy the
+        planner owns and refreshes); the margin, the skip and the point mask are clear_margin, clear_skip and scene_mask; the
+        pinned rows are the in-painted ones.  It composes with num_samples / select unchanged.  self.last_guidance =
+        Guidance(steps = the guided positions, nearest = the distances the LAST guide step found before its push, (B, G, L) or
+        (B, L)).  None (default): today's launches and today's bits."""
         head = self.prediction_head
         dev = pcd_obs.device
         B, Ln = trajectory_mask.shape
@@ -1189,6 +1323,12 @@ class DiffusionPlanner(nn.Module):
                 raise ValueError("step_noise has %d leading rows for a schedule of %d steps (one row per step position)"
                                  % (step_noise.shape[0], K))
         D = curr_gripper.shape[-1] + 2
+        guide = check_guide(guide)
+        if guide is not None:
+            check_guide_shape(G or 1, Ln, D)
+            g_cam, g_pix = check_scene(pcd_obs, scene_mask, B)
+            g_margin, g_sh, g_st = check_clearance_args(clear_margin, clear_skip)
+            g_mask = trajectory_mask                                    # per scene: the fallback paths below expand their own copy
         if G is not None:
             check_candidate_noise(init_noise, step_noise, B, G, Ln, D, K if scheduled else self.n_steps)
 
@@ -1261,7 +1401,9 @@ class DiffusionPlanner(nn.Module):
             sched_key = (sched_key, "num_samples", G, "group" if group else "expanded")
         if fused_conditioning:
             sched_key = (sched_key, "fused_conditioning")
-        else:
+        if guide is not None:
+            sched_key = (sched_key, "guide") + guide + (g_margin, g_sh, g_st, scene_mask is not None)
+        if not fused_conditioning:
             traj = (init_noise.to(dev).float() + cond_data).contiguous()
 
         # ---- step-invariant state of the planned path; `static` is what a captured graph refreshes in place
@@ -1283,8 +1425,20 @@ class DiffusionPlanner(nn.Module):
         static = static + ([] if step_noise is None else [step_noise]) + [cond_data, cond_mask_u8, kmask]
         if sched is not None:
             static = static + [sched.coef_pos, sched.coef_rot]
-        key = (B, Ln, plan.steps, plan.path, tuple((tuple(t_.shape), t_.dtype) for t_ in static), sched_key)
         replay = use_graph and not return_trace
+        if guide is not None:
+            # what the guide pair reads: the caller's cloud and masks in place; a captured graph addresses copies the planner owns,
+            # refreshed with the other static inputs, so a replay sees this call's cloud and never writes into the caller's tensor
+            g_S = _scene_planar(pcd_obs)
+            g_in = [g_S, _mask_bytes(g_mask)] + ([] if scene_mask is None else [_mask_bytes(scene_mask)])
+            g_bounds = O._c(self.gripper_loc_bounds)
+            static = static + g_in
+        key = (B, Ln, plan.steps, plan.path, tuple((tuple(t_.shape), t_.dtype) for t_ in static), sched_key)
+        if guide is not None:
+            if replay and (self._graph is None or self._graph["key"] != key):       # this call captures: the copies are made once
+                g_in = [t_.clone() for t_ in g_in]
+                static[-len(g_in):] = g_in
+            g_S, g_tm, g_sm = g_in[0], g_in[1], (g_in[2] if len(g_in) > 2 else None)
         if plan.path == "persistent":
             # a replay of the captured loop addresses the state retained in self._graph: no second set of persistent-sampler buffers
             # (a ctypes table, a pageable host-to-device copy = a host sync, five allocations) that would be thrown away
@@ -1298,11 +1452,37 @@ class DiffusionPlanner(nn.Module):
         self.last_sampler_path = plan.label                 # which sampler serves this call (read by the bench line and the tests)
         trace = []
 
+        n_exec = len(plan.steps)
+        segments = guided_segments(n_exec, None if guide is None else guide[2])
+        g_out = {}
+
+        def guide_step(x, last):
+            # x is the tensor the step just produced (every path returns a new one): updated in place, stream-ordered
+            if "ws" not in g_out:
+                g_out["ws"] = torch.empty((O.L.load().a3d_traj_guide_ws_floats(B_scene, G or 1, Ln, g_cam * g_pix, 0),), device=dev,
+                                          dtype=torch.float32)
+            nearest = torch.empty((B_scene, G, Ln) if G is not None else (B_scene, Ln), device=dev, dtype=torch.float32) if last else None
+            _guide_launch(x, g_tm, cond_mask_u8, g_bounds, g_S, g_sm, g_cam, g_pix, g_margin, g_sh, g_st, guide[0], guide[1], nearest,
+                          g_out["ws"], B_scene, G or 1, Ln)
+            if last:
+                g_out["nearest"] = nearest
+
         def run(x):
-            if plan.path == "persistent" and not return_trace:      # the whole loop: one launch
-                return head.fused_persist(state, x, 0 if plan.scheduled else plan.steps[0], len(plan.steps), step_noise, cond_data,
-                                          cond_mask_u8, tables)
-            for i, t in enumerate(plan.steps):
+            g_out.pop("ws", None)                           # a workspace per run: a captured one belongs to the graph's pool
+            for first, count, guided in segments:
+                x = run_steps(x, first, count, guided)
+            return x
+
+        def run_steps(x, first, count, guided):
+            """the steps at positions first .. first + count - 1 of plan.steps; guided (count = 1): then the guide pair"""
+            if plan.path == "persistent" and not return_trace:      # the whole run of steps: one launch
+                x = head.fused_persist(state, x, first if plan.scheduled else plan.steps[first], count, step_noise, cond_data,
+                                       cond_mask_u8, tables)
+                if guided:
+                    guide_step(x, first == n_exec - 1)
+                return x
+            for i in range(first, first + count):
+                t = plan.steps[i]
                 # a schedule addresses its tables and its noise by step POSITION and names its terminal step (timestep 0, position
                 # K - 1); the full chain addresses them by timestep.  No step at timestep 0 reads noise.
                 row, term = (i, t == 0) if plan.scheduled else (t, None)
@@ -1321,11 +1501,20 @@ class DiffusionPlanner(nn.Module):
                         x = O.ddpm_step(out, x, nz, cond_data, cond_mask_u8, tables.coef_pos, tables.coef_rot, row)
                     else:
                         x = O.ddpm_step_sched(out, x, nz, cond_data, cond_mask_u8, tables.coef_pos, tables.coef_rot, row, term)
+                if guided:
+                    guide_step(x, i == n_exec - 1)
                 if return_trace:
                     trace.append(x)
             return x
 
         traj = self._replay(key, run, traj, static, state) if replay else run(traj)
+        self.last_guidance = None
+        if guide is not None:
+            nearest = g_out.get("nearest")
+            if replay:
+                # the captured guide pair writes the tensor of the capturing call: kept with the graph, handed out as a copy
+                nearest = self._graph.setdefault("guide_nearest", nearest).clone()
+            self.last_guidance = Guidance(tuple(i for i, _, guided in segments if guided), nearest)
 
         # ---- poses, candidates, ranking
         final = signal_to_pose(traj, self.gripper_loc_bounds)

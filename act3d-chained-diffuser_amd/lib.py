@@ -92,6 +92,8 @@ SIGNATURES = {
     "a3d_traj_rank_extra": (_i, [_p, _p, _p, _i, _p] + [_f] * 6 + [_p] * 5 + [_i] * 4 + [_p, _f, _p]),
     "a3d_traj_clearance_ws_floats": (_z, [_i] * 5),
     "a3d_traj_clearance": (_i, [_p, _p, _p, _p, _i, _i, _f, _i, _i, _p, _p, _p] + [_i] * 5 + [_p]),
+    "a3d_traj_guide_ws_floats": (_z, [_i] * 5),
+    "a3d_traj_guide": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _f, _i, _i, _f, _f, _p, _p] + [_i] * 4 + [_p]),
     "a3d_traj_errors": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "a3d_keypose_errors": (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
     "a3d_sym_quat_loss": (_i, [_p, _p, _i, _f, _p, _p, _i, _p]),

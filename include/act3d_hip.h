@@ -497,6 +497,29 @@ size_t a3d_traj_clearance_ws_floats(int B, int G, int L, int n_points, int n_chu
 int a3d_traj_clearance(const float* poses, const unsigned char* tmask, const float* scene, const unsigned char* scene_mask, int n_cam,
                        int n_pix, float margin, int skip_head, int skip_tail, float* nearest, float* clearance, float* ws,
                        int n_chunks, int B, int G, int L, int Dp, void* stream);
+/* One clearance-guidance step on trajectory SIGNALS, in place, in two launches (csrc/traj_guide.hip).  None in the reference.
+ * traj: [B][G][L][D] fp32 signals, scene-major, D = 9 or 10; only channels 0..2 (positions normalised to bounds) are read or
+ * written.  tmask, scene, scene_mask, n_cam, n_pix, margin, skip_head, skip_tail, "counted point" and d^2: as a3d_traj_clearance.
+ * cond_mask: NULL or [B G][L][D] bytes, the sampler's in-painting mask (byte 0 of a row is read); bounds: device [2][3] = lo, hi.
+ *   world position   p = ((x + 1) * 0.5) * (hi - lo) + lo, this fp32 expression, not contracted
+ *   free row         valid, skip_head <= j < n - skip_tail (j = rank among the scene's n valid rows), cond_mask[row][0] == 0, p finite
+ *   push             s* = the counted point of smallest d^2, ties to the smallest index n = c n_pix + pixel; d = sqrt(d^2);
+ *                    u = push (margin - d) (p - s*) / d when 0 < d < margin, else 0 (d == 0 and no counted point included):
+ *                    push = 1 puts the waypoint on the margin sphere of its nearest point
+ *   smooth           v = smooth ((p_prev + p_next) / 2 - p), prev / next = the neighbouring VALID rows by rank (pinned rows count),
+ *                    every position read before any update; 0 when a neighbour is missing or not finite
+ *   update           x' = x + (u + v) 2 / (hi - lo) per coordinate on the free rows, stored only where the addend is not 0; every
+ *                    other row and channel keeps its bits
+ *   nearest[b][g][i] NULL or d before the push: +inf without a counted point and on padded rows, NaN where p is not finite
+ * ws: a3d_traj_guide_ws_floats(B, G, L, N, n_chunks) floats owned by the caller (partial minima: d^2 and the index), n_chunks as
+ * a3d_traj_clearance.  The minimum is exact and the tie rule total: bit-identical from run to run and for every n_chunks; no
+ * atomics.  Stream-ordered, no host synchronisation, capturable.  margin finite and > 0; skips >= 0; push and smooth in [0, 1], not
+ * both 0; G <= 64; L <= 256; B <= 65535. */
+size_t a3d_traj_guide_ws_floats(int B, int G, int L, int n_points, int n_chunks);
+int a3d_traj_guide(float* traj, int D, const unsigned char* tmask, const unsigned char* cond_mask, const float* bounds,
+                   const float* scene, const unsigned char* scene_mask, int n_cam, int n_pix, float margin, int skip_head,
+                   int skip_tail, float push, float smooth, float* nearest, float* ws, int n_chunks, int B, int G, int L,
+                   void* stream);
 /* cols[b][9] of TrajectoryCriterion.compute_metrics (main_trajectory.py:303-343), see diffusion.hip; pred, gt: [B][L][D], D >= 7. */
 int a3d_traj_errors(const float* pred, const float* gt, float* cols, int B, int L, int D, void* stream);
 /* cols[b][6 + nlev] of LossAndMetrics.compute_metrics (main_keypose.py:431-482), see heads.hip; pos: [nlev + 1][B][3] with
