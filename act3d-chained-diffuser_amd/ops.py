@@ -4,6 +4,7 @@ backward launches of libact3d_hip.so.  PyTorch only provides device memory, the 
 Parameter gradients are accumulated by the wgrad kernels straight into ``param.grad`` (the flat gradient buffer
 when the model is wrapped by ``FlatParams``) instead of being returned through autograd; see DESIGN.md.
 """
+import collections
 import ctypes
 import math
 import os
@@ -314,35 +315,241 @@ def _rows_only():
     return ROWS_ONLY and ATTN_MODE != "fp8"
 
 
-def _alloc16(B, H, Lqp, Sp, device, need_bwd):
-    hf = torch.float16
-    Qr = torch.empty((B, H, Lqp, 32), device=device, dtype=hf)       # rows16: hi | lo
-    Kr = torch.empty((B, H, Sp, 32), device=device, dtype=hf)
-    if _rows_only():
-        return Qr, Kr, None, None, None, torch.empty((B, H, Sp, 32), device=device, dtype=hf)
-    Vp = torch.empty((B, H, 2, 16, Sp), device=device, dtype=hf)     # planes16: hi and lo planes, transposed
-    Vr = None
-    if need_bwd:
-        Vr = torch.empty((B, H, Sp, 32), device=device, dtype=hf)
-    return Qr, Kr, Vp, None, None, Vr                                # (q / k planes: not read by any kernel since round 6)
+FUSED_PROJ = os.environ.get("A3D_FUSED_PROJ", "1") == "1"
+
+
+def _fused_proj(E):
+    """Whether a3d_proj_rope_split[16] serves an in-projection of width E: q | k | v = x W^T + b computed per 64-row tile and written
+    straight in the operand formats (the projected rows never reach HBM); else a linear launch, then RoPE + operand formatting."""
+    return FUSED_PROJ and E % 4 == 0 and E <= 128
+
+
+# The packed in-projection of an attention block (DESIGN.md section 4.20).  Per mode -- "kv": key is value, packed k,v projection
+# (multihead_custom_attention.py:251-275); "qk": query is key, value differs (:277-303); "none": three inputs -- a list of GROUPS
+# (index of the input in (q_in, k_in, v_in), first E-row block of in_proj_weight, roles).  A group is ONE GEMM over one input: it covers
+# len(roles) consecutive E-row blocks of in_proj_weight and writes the roles' operands; the backward reads the roles' gradients side by
+# side from one [rows, len(roles) E] buffer.  A role fixes its rotation (q_xyz / k_xyz / none), its scale (the softmax scale on q --
+# times log2 e in the fp16 family, whose scores are in log2 units -- else 1.0) and its row count (Lq, else S).  Forward writer, backward
+# loop, the cached inference pair and attn_block_plan all iterate this table.
+PROJ_GROUPS = {
+    "kv": ((0, 0, ("q",)), (1, 1, ("k", "v"))),
+    "qk": ((0, 0, ("q", "k")), (2, 2, ("v",))),
+    "none": ((0, 0, ("q",)), (1, 1, ("k",)), (2, 2, ("v",))),
+}
+Role = collections.namedtuple("Role", "xyz scale n npad grad nsplit", defaults=(None, 1))   # grad, nsplit: the backward's, from the core
+Slot = collections.namedtuple("Slot", "rows planes word", defaults=(None,) * 3)             # a role's operands (alloc_operands)
+
+
+def group_layout(w0, roles, E):
+    """-> (byte offset of the group's rows in in_proj_weight, in in_proj_bias, byte offset of each role's column slice in the group's
+    fp32 rows, their leading dimension in floats).  The one place the pointer arithmetic of the packed projection is done."""
+    return w0 * E * E * 4, w0 * E * 4, tuple(i * E * 4 for i in range(len(roles))), len(roles) * E
+
+
+def alloc_operands(f16, roles, B, H, Lqp, Sp, device, need_bwd):
+    """-> {role: Slot}: the operand slots of `roles` in one family.  word is what the split kernels take next to the two pointers:
+    the rows width of the bf16 family (QKW for q / k: hi | lo | lo2, 32 for v) or the plane parts of the fp16 family (PLANE_PARTS,
+    V_ROWS, V_PLANES).  bf16: q / k rows and v planes serve the forward, the other format of each the backward.
+    fp16: q / k rows alone (no kernel reads q / k planes); v rows in the rows-only set, else v planes plus the rows the backward reads."""
+    dt = torch.float16 if f16 else torch.bfloat16
+    rows = lambda n, w: torch.empty((B, H, n, w), device=device, dtype=dt)
+    planes = lambda n: torch.empty((B, H, 2, 16, n), device=device, dtype=dt)    # hi and lo planes, transposed
+    slots = {}
+    for r in roles:
+        n = Lqp if r == "q" else Sp
+        if r != "v":
+            slots[r] = Slot(rows(n, 32), None, PLANE_PARTS) if f16 else Slot(rows(n, QKW), planes(n) if need_bwd else None, QKW)
+        elif f16 and _rows_only():
+            slots[r] = Slot(rows(n, 32), None, V_ROWS)
+        else:
+            slots[r] = Slot(rows(n, 32) if need_bwd else None, planes(n), V_PLANES if f16 else 32)
+    return slots
+
+
+def write_operands(f16, groups, role, slots, freq, B, E, H, device, x=None, wp=None, bp=None, fused=True, pre=None):
+    """Write the operands of `groups` (entries of PROJ_GROUPS) into `slots`.  role: {role: Role}; slots: {role: Slot}; x: the (q_in,
+    k_in, v_in) inputs; wp / bp: device pointers of in_proj_weight [3E][E] / in_proj_bias [3E].
+    fused: one a3d_proj_rope_split[16] per group (blk0, blk1 = the group's roles).  Else one linear launch per group, then one
+    a3d_rope_split[16] per role on its column slice; pre = {role: (pointer, leading dimension)} names rows that are projected already."""
+    st, fp = L.stream(), freq.data_ptr()
+    nz = lambda t: None if t is None else t.data_ptr()
+
+    def blk(r):                                  # a role's launch arguments: xyz, scale, its slot in the family's order
+        xyz, scale, s = nz(role[r].xyz), role[r].scale, slots[r]
+        return (xyz, scale, nz(s.rows), nz(s.planes), s.word) if f16 else (xyz, scale, nz(s.rows), s.word, nz(s.planes))
+
+    if fused:
+        absent = (None, 1.0, None, None, 1) if f16 else (None, 1.0, None, 32, None)
+        for src, w0, roles in groups:
+            w_off, b_off, _, _ = group_layout(w0, roles, E)
+            first = role[roles[0]]
+            L.call("a3d_proj_rope_split16" if f16 else "a3d_proj_rope_split", x[src].data_ptr(), E, wp + w_off, E, bp + b_off, E,
+                   *blk(roles[0]), *(blk(roles[1]) if len(roles) > 1 else absent), fp, B, first.n, first.npad, E, H, st)
+        return
+    keep = []
+    if pre is None:
+        pre = {}
+        for src, w0, roles in groups:
+            w_off, b_off, cols, ld = group_layout(w0, roles, E)
+            keep.append(linear_raw(x[src].data_ptr(), E, wp + w_off, E, bp + b_off, B * role[roles[0]].n, ld, E, device))
+            pre.update((r, (keep[-1].data_ptr() + c, ld)) for r, c in zip(roles, cols))
+    for r in (r for r in "qkv" if r in pre):
+        xyz, *rest = blk(r)                                      # freq goes between xyz and scale here
+        L.call("a3d_rope_split16" if f16 else "a3d_rope_split", *pre[r], xyz, fp, *rest, B, role[r].n, role[r].npad, E, H, st)
+
+
+def _operands(f16, groups, x, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd, fused=True, pre=None, kv_pair=None):
+    """Allocate and write the operands of `groups` -> (Qs, Ks, Vt, Lqp, Sp, scale, freq, extra): q rows, k rows, the value operand the
+    forward reads (planes; the rows of the rows-only set), and extra = (q planes, k planes, v rows) for the backward -- (Qt, Kt, Vs) in
+    the bf16 family, (None, None, Vr) in the fp16 family.  `scale` is the factor a3d_rope_merge_bwd applies to the q gradient.
+    kv_pair: the (Kr, Vr) rows ops.ctx_kv_operands16 wrote for this layer (fp16 rows-only slots that no group here writes)."""
+    Lqp, Sp = ceil_to(Lq, 64), ceil_to(S, 64)
+    scale = float(E // H) ** -0.5 * (LOG2E if f16 else 1.0)
+    freq = rope_freq(E, device)
+    role = {"q": Role(q_xyz, scale, Lq, Lqp), "k": Role(k_xyz, 1.0, S, Sp), "v": Role(None, 1.0, S, Sp)}
+    written = list(pre) if pre is not None else [r for _, _, roles in groups for r in roles]
+    slots = alloc_operands(f16, written, B, H, Lqp, Sp, device, need_bwd)
+    if kv_pair is not None:
+        slots["k"], slots["v"] = Slot(kv_pair[0], None, PLANE_PARTS), Slot(kv_pair[1], None, V_ROWS)
+    write_operands(f16, groups, role, slots, freq, B, E, H, device, x, wp, bp, fused, pre)
+    q, k, v = (slots.get(r, Slot()) for r in "qkv")
+    return q.rows, k.rows, (v.rows if v.planes is None else v.planes), Lqp, Sp, scale, freq, (q.planes, k.planes, v.rows)
+
+
+def attn_operands(q_pre_ptr, ldq, k_pre_ptr, ldk, v_pre_ptr, ldv, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False):
+    """rope + split three projected row sets into the operand formats of the bf16x3 kernels (a3d_rope_split)."""
+    return _operands(False, (), None, None, None, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd, fused=False,
+                     pre={"q": (q_pre_ptr, ldq), "k": (k_pre_ptr, ldk), "v": (v_pre_ptr, ldv)})
 
 
 def attn_operands16(q_pre_ptr, ldq, k_pre_ptr, ldk, v_pre_ptr, ldv, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False):
-    """attn_operands for the split-fp16 kernels: q carries scale * log2(e) (scores in log2 units); returns the same tuple
-    shape, `scale` being the factor a3d_rope_merge_bwd must apply to the q gradient."""
+    """attn_operands for the split-fp16 kernels (a3d_rope_split16): q carries scale * log2(e)."""
+    return _operands(True, (), None, None, None, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd, fused=False,
+                     pre={"q": (q_pre_ptr, ldq), "k": (k_pre_ptr, ldk), "v": (v_pre_ptr, ldv)})
+
+
+def attn_operands_fused(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False):
+    """attn_operands with the in-projections folded in (a3d_proj_rope_split)."""
+    return _operands(False, PROJ_GROUPS[mode], (q_in, k_in, v_in), wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd)
+
+
+def attn_operands_fused16(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False, kv_pair=None):
+    """attn_operands_fused for the split-fp16 kernels (a3d_proj_rope_split16).  kv_pair: the (Kr, Vr) rows of this layer already
+    written by ctx_kv_operands16 (mode "kv", rows-only set): only the q group is written here."""
+    groups = PROJ_GROUPS[mode] if kv_pair is None else PROJ_GROUPS[mode][:1]
+    return _operands(True, groups, (q_in, k_in, v_in), wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd, kv_pair=kv_pair)
+
+
+def _core_fwd_entry(f16, rows, dropping, need_bwd):
+    """The forward core for fp16 / bf16 operands, value rows (the rows-only set) / planes."""
+    if not f16:
+        return "a3d_attn_fwd_dropout" if dropping else "a3d_attn_fwd"
+    if ATTN_MODE == "fp8" and not dropping and not need_bwd:
+        return "a3d_attn8_fwd"
+    return "a3d_attn16_fwd_rows" if rows else "a3d_attn16_fwd"
+
+
+def _core_bwd_entry(f16, dropping):
+    if f16:
+        return "a3d_attn16_bwd"
+    return "a3d_attn_bwd_bf16_dropout" if dropping else "a3d_attn_bwd_bf16"
+
+
+def _group_grad_route(roles, needs, sink, fold_q):
+    """What becomes of a group's input gradient in the backward.  needs: whether (q_in, k_in, v_in) need one; sink: a GradSink takes
+    the context's; fold_q: the query is the residual stream and its gradient is wanted.
+    "parked": the group's rows wait in the sink's shared buffer, the gate issues both of its GEMMs; "sink": written / added into the
+    sink's buffer; "fold": added into the LayerNorm's input gradient; "fresh": a tensor of its own; None: no input needs it."""
+    if sink and "k" in roles:
+        return "parked" if CTX_DEFER else "sink"
+    if not any(needs["qkv".index(r)] for r in roles):
+        return None
+    return "fold" if fold_q and "q" in roles else "fresh"
+
+
+REDUCE_TABLE_LAUNCHES = ["a3d_grad_reduce_table_plan", "a3d_grad_reduce_table_upload", "a3d_grad_reduce_table"]
+
+
+class AttnRoute:
+    """What serves one AttnBlockFn call (attn_block_plan): plain strings and numbers, nothing launched.
+    family      "f16" (split-fp16 operands and kernels), "fp8" (the same operands, e4m3 forward core) or "bf16x3"
+    operands    "rows" (the rows-only set) or "rows+planes"
+    projection  "context" (k | v rows precomputed by ctx_kv_operands16, only q is projected), "fused" or "unfused"
+    groups      the entries of PROJ_GROUPS the forward writes
+    core_fwd / core_bwd   entry names (core_bwd: None when no backward can follow);  nsplit: key-range splits of both"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def f16(self):
+        return self.family != "bf16x3"
+
+    def _wgrad(self, M, N, K):
+        two_stage = L.load().a3d_linear_wgrad_ws_bytes(M, N, K, 1) > 0
+        return "a3d_linear_wgrad_partials" if two_stage and self.queue else "a3d_linear_wgrad_ws"
+
+    def launches_forward(self):
+        """Entry names of the forward's launches in order: projection, core, out-projection (+ residual dropout), add & LayerNorm."""
+        n = len(self.groups)
+        if self.projection == "unfused":
+            out = ["a3d_linear_fwd"] * n + ["a3d_rope_split16" if self.f16 else "a3d_rope_split"] * 3
+        else:
+            out = ["a3d_proj_rope_split16" if self.f16 else "a3d_proj_rope_split"] * n
+        out.append(self.core_fwd)
+        if self.dropping:
+            out += ["a3d_linear_fwd_drop"] if DROP_FOLD else ["a3d_linear_fwd", "a3d_dropout"]
+        else:
+            out.append("a3d_linear_fwd")
+        return out + ["a3d_add_layernorm_fwd"]
+
+    def launches_backward(self):
+        """Entry names of the backward's launches in order: LayerNorm (+ residual dropout), out-projection dgrad and wgrad, core, then
+        per group the inverse rotations, the weight gradient and the input gradient.  The switches the backward reads (CTX_DEFER,
+        DROP_FOLD, DEFER_REDUCE) are read now; a flush of the reduce queue and the sink gate's launches are not the block's."""
+        B, Lq, S, E = self.B, self.Lq, self.S, self.E
+        if not self.need_bwd:
+            return []
+        if DEFER_REDUCE and L.load().a3d_add_layernorm_bwd_partials_count(B * Lq, E) > 0:
+            out = ["a3d_add_layernorm_bwd_partials"] + ([] if self.queue else REDUCE_TABLE_LAUNCHES)
+            out += ["a3d_dropout"] if self.dropping else []
+        elif self.dropping:
+            out = ["a3d_add_layernorm_bwd_drop"] if DROP_FOLD else ["a3d_add_layernorm_bwd", "a3d_dropout"]
+        else:
+            out = ["a3d_add_layernorm_bwd"]
+        out += ["a3d_linear_fwd", self._wgrad(B * Lq, E, E), self.core_bwd]
+        for _, _, roles in PROJ_GROUPS[self.mode]:
+            to = _group_grad_route(roles, self.needs, self.sink, self.q_is_resid and self.needs[3])
+            out += ["a3d_rope_merge_bwd"] * len(roles)
+            if to != "parked":
+                out.append(self._wgrad(B * (Lq if roles[0] == "q" else S), len(roles) * E, E))
+                out += ["a3d_linear_fwd"] if to else []
+        return out
+
+
+def attn_block_plan(mode, B, Lq, S, E, H, need_bwd=True, dropping=False, kv_pair=False, sink=False, q_is_resid=False,
+                    needs=(True, True, True, True), queue=False):
+    """Host side of AttnBlockFn, in the manner of nn.backbone_plan: the route one block takes, decided from the shapes, the module
+    switches (read now) and the library's size queries alone.  need_bwd: a backward can follow; dropping: dropout with p > 0;
+    kv_pair: the caller supplies this layer's context rows (ctx_kv_applicable held); sink: a GradSink of the context's shape is
+    offered; needs: which of (q_in, k_in, v_in, resid) need a gradient; queue: a ReduceQueue would accept the backward's records."""
+    if kv_pair and mode != "kv":
+        raise RuntimeError("AttnBlockFn: precomputed context operands need the packed k,v projection (key is value)")
+    f16 = bool(kv_pair) or _use16(Lq, need_bwd)
+    rows = bool(kv_pair) or (f16 and _rows_only())
     Lqp, Sp = ceil_to(Lq, 64), ceil_to(S, 64)
-    scale = float(E // H) ** -0.5 * LOG2E
-    freq = rope_freq(E, device)
-    Qr, Kr, Vp, Qp, Kp, Vr = _alloc16(B, H, Lqp, Sp, device, need_bwd)
-    st = L.stream()
-    qx = None if q_xyz is None else q_xyz.data_ptr()
-    kx = None if k_xyz is None else k_xyz.data_ptr()
-    nz = lambda t: None if t is None else t.data_ptr()
-    L.call("a3d_rope_split16", q_pre_ptr, ldq, qx, freq.data_ptr(), scale, Qr.data_ptr(), nz(Qp), PLANE_PARTS, B, Lq, Lqp, E, H, st)
-    L.call("a3d_rope_split16", k_pre_ptr, ldk, kx, freq.data_ptr(), 1.0, Kr.data_ptr(), nz(Kp), PLANE_PARTS, B, S, Sp, E, H, st)
-    L.call("a3d_rope_split16", v_pre_ptr, ldv, None, freq.data_ptr(), 1.0, nz(Vr), nz(Vp), V_ROWS if Vp is None else V_PLANES,
-           B, S, Sp, E, H, st)
-    return Qr, Kr, (Vr if Vp is None else Vp), Lqp, Sp, scale, freq, (Qp, Kp, Vr)
+    core_fwd = _core_fwd_entry(f16, rows, dropping, need_bwd)
+    return AttnRoute(
+        mode=mode, B=B, Lq=Lq, S=S, E=E, H=H, need_bwd=bool(need_bwd), dropping=bool(dropping), needs=tuple(needs),
+        q_is_resid=bool(q_is_resid), queue=bool(queue),
+        family="bf16x3" if not f16 else "fp8" if core_fwd == "a3d_attn8_fwd" else "f16",
+        operands="rows" if rows else "rows+planes",
+        projection="context" if kv_pair else "fused" if _fused_proj(E) else "unfused",
+        groups=PROJ_GROUPS[mode][:1] if kv_pair else PROJ_GROUPS[mode],
+        core_fwd=core_fwd, core_bwd=_core_bwd_entry(f16, dropping) if need_bwd else None,
+        nsplit=pick_nsplit(B, H, Lqp, Sp),
+        # the context's gradient goes into its shared buffer (packed k,v projection of ONE input only: a single dgrad GEMM)
+        sink=bool(sink and need_bwd and mode == "kv" and needs[1]))
 
 
 # One launch for the k | v blocks of every attention layer that reads one context (csrc/ctx_proj.hip, a3d_ctx_kv_proj16): the two
@@ -357,7 +564,7 @@ def ctx_kv_applicable(value, value_xyz, mhas, H, Lq=1):
     model, fp32 device tensors, at most CTX_KV_MAX_LAYERS layers.  (Lq: the query count; a block whose backward would exceed the
     split-fp16 backward's query limit runs on the bf16x3 family, whichever grad mode -- the operands must suit both passes.)"""
     E = value.shape[-1]
-    if not (CTX_KV_BATCH and FUSED_PROJ and _rows_only() and _use16(Lq, True) and E == 60 and H == 4):
+    if not (CTX_KV_BATCH and _fused_proj(E) and _rows_only() and _use16(Lq, True) and E == 60 and H == 4):
         return False
     if not (1 <= len(mhas) <= CTX_KV_MAX_LAYERS and value.is_cuda and value.dtype == F32 and value.dim() == 3):
         return False
@@ -391,115 +598,6 @@ def ctx_kv_operands16(value, value_xyz, mhas, H):
     L.call("a3d_ctx_kv_proj16", value.data_ptr(), E, None if xyz is None else xyz.data_ptr(), *args, E, freq.data_ptr(), len(mhas),
            B, S, Sp, E, H, 0, L.stream())
     return pairs
-
-
-def attn_operands_fused16(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False, kv_pair=None):
-    """attn_operands_fused for the split-fp16 kernels (a3d_proj_rope_split16).  kv_pair: the (Kr, Vr) rows of this layer already
-    written by ctx_kv_operands16 (mode "kv", rows-only set): only q is projected here."""
-    Lqp, Sp = ceil_to(Lq, 64), ceil_to(S, 64)
-    scale = float(E // H) ** -0.5 * LOG2E
-    freq = rope_freq(E, device)
-    if kv_pair is not None:
-        Kr, Vr = kv_pair
-        Qr = torch.empty((B, H, Lqp, 32), device=device, dtype=torch.float16)
-        L.call("a3d_proj_rope_split16", q_in.data_ptr(), E, wp, E, bp, E,
-               None if q_xyz is None else q_xyz.data_ptr(), scale, Qr.data_ptr(), None, PLANE_PARTS, None, 1.0, None, None, 1,
-               freq.data_ptr(), B, Lq, Lqp, E, H, L.stream())
-        return Qr, Kr, Vr, Lqp, Sp, scale, freq, (None, None, Vr)
-    Qr, Kr, Vp, Qp, Kp, Vr = _alloc16(B, H, Lqp, Sp, device, need_bwd)
-    st = L.stream()
-    f4 = 4
-    qx = None if q_xyz is None else q_xyz.data_ptr()
-    kx = None if k_xyz is None else k_xyz.data_ptr()
-    nz = lambda t: None if t is None else t.data_ptr()
-    fp = freq.data_ptr()
-
-    def proj(x, w_off, blk0, blk1, N, Npad):
-        L.call("a3d_proj_rope_split16", x.data_ptr(), E, wp + w_off * E * f4, E, bp + w_off * f4, E,
-               *blk0, *(blk1 if blk1 is not None else (None, 1.0, None, None, 1)), fp, B, N, Npad, E, H, st)
-
-    qb = (qx, scale, Qr.data_ptr(), nz(Qp), PLANE_PARTS)
-    kb = (kx, 1.0, Kr.data_ptr(), nz(Kp), PLANE_PARTS)
-    vb = (None, 1.0, nz(Vr), nz(Vp), V_ROWS if Vp is None else V_PLANES)
-    if mode == "qk":
-        proj(q_in, 0, qb, kb, Lq, Lqp)
-        proj(v_in, 2 * E, vb, None, S, Sp)
-    else:
-        proj(q_in, 0, qb, None, Lq, Lqp)
-        if mode == "kv":
-            proj(k_in, E, kb, vb, S, Sp)
-        else:
-            proj(k_in, E, kb, None, S, Sp)
-            proj(v_in, 2 * E, vb, None, S, Sp)
-    return Qr, Kr, (Vr if Vp is None else Vp), Lqp, Sp, scale, freq, (Qp, Kp, Vr)
-
-
-def attn_operands(q_pre_ptr, ldq, k_pre_ptr, ldk, v_pre_ptr, ldv, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False):
-    """rope + split the three projected row sets into the attention operand formats.  The forward reads q and k in the
-    rows (QK) format and v in the planes (VT) format; the bf16 backward additionally needs the other format of each
-    (returned in `extra` = (Qt, Kt, Vs)), written by the same pass."""
-    Lqp, Sp = ceil_to(Lq, 64), ceil_to(S, 64)
-    scale = float(E // H) ** -0.5
-    freq = rope_freq(E, device)
-    bf = torch.bfloat16
-    Qs = torch.empty((B, H, Lqp, QKW), device=device, dtype=bf)     # q, k rows: hi | lo | lo2
-    Ks = torch.empty((B, H, Sp, QKW), device=device, dtype=bf)
-    Vt = torch.empty((B, H, 2, 16, Sp), device=device, dtype=bf)
-    Qt = Kt = Vs = None
-    if need_bwd:
-        Qt = torch.empty((B, H, 2, 16, Lqp), device=device, dtype=bf)
-        Kt = torch.empty((B, H, 2, 16, Sp), device=device, dtype=bf)
-        Vs = torch.empty((B, H, Sp, 32), device=device, dtype=bf)
-    st = L.stream()
-    qx = None if q_xyz is None else q_xyz.data_ptr()
-    kx = None if k_xyz is None else k_xyz.data_ptr()
-    nz = lambda t: None if t is None else t.data_ptr()
-    L.call("a3d_rope_split", q_pre_ptr, ldq, qx, freq.data_ptr(), scale, Qs.data_ptr(), QKW, nz(Qt), B, Lq, Lqp, E, H, st)
-    L.call("a3d_rope_split", k_pre_ptr, ldk, kx, freq.data_ptr(), 1.0, Ks.data_ptr(), QKW, nz(Kt), B, S, Sp, E, H, st)
-    L.call("a3d_rope_split", v_pre_ptr, ldv, None, freq.data_ptr(), 1.0, nz(Vs), 32, Vt.data_ptr(), B, S, Sp, E, H, st)
-    return Qs, Ks, Vt, Lqp, Sp, scale, freq, (Qt, Kt, Vs)
-
-
-FUSED_PROJ = os.environ.get("A3D_FUSED_PROJ", "1") == "1"
-
-
-def attn_operands_fused(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, device, need_bwd=False):
-    """attn_operands with the in-projections folded in (a3d_proj_rope_split): q | k | v = x W^T + b computed per 64-row
-    tile and written straight in the operand formats.  wp / bp: device pointers of in_proj_weight [3E][E] / bias [3E]."""
-    Lqp, Sp = ceil_to(Lq, 64), ceil_to(S, 64)
-    scale = float(E // H) ** -0.5
-    freq = rope_freq(E, device)
-    bf = torch.bfloat16
-    Qs = torch.empty((B, H, Lqp, QKW), device=device, dtype=bf)
-    Ks = torch.empty((B, H, Sp, QKW), device=device, dtype=bf)
-    Vt = torch.empty((B, H, 2, 16, Sp), device=device, dtype=bf)
-    Qt = Kt = Vs = None
-    if need_bwd:
-        Qt = torch.empty((B, H, 2, 16, Lqp), device=device, dtype=bf)
-        Kt = torch.empty((B, H, 2, 16, Sp), device=device, dtype=bf)
-        Vs = torch.empty((B, H, Sp, 32), device=device, dtype=bf)
-    st = L.stream()
-    f4 = 4
-    qx = None if q_xyz is None else q_xyz.data_ptr()
-    kx = None if k_xyz is None else k_xyz.data_ptr()
-    nz = lambda t: None if t is None else t.data_ptr()
-    fp = freq.data_ptr()
-
-    def proj(x, w_off, blk0, blk1, N, Npad):
-        L.call("a3d_proj_rope_split", x.data_ptr(), E, wp + w_off * E * f4, E, bp + w_off * f4, E,
-               *blk0, *(blk1 if blk1 is not None else (None, 1.0, None, 32, None)), fp, B, N, Npad, E, H, st)
-
-    if mode == "qk":        # q and k from the same rows (packed q,k projection), v separately
-        proj(q_in, 0, (qx, scale, Qs.data_ptr(), QKW, nz(Qt)), (kx, 1.0, Ks.data_ptr(), QKW, nz(Kt)), Lq, Lqp)
-        proj(v_in, 2 * E, (None, 1.0, nz(Vs), 32, Vt.data_ptr()), None, S, Sp)
-    else:
-        proj(q_in, 0, (qx, scale, Qs.data_ptr(), QKW, nz(Qt)), None, Lq, Lqp)
-        if mode == "kv":    # packed k,v projection of the shared key/value rows
-            proj(k_in, E, (kx, 1.0, Ks.data_ptr(), QKW, nz(Kt)), (None, 1.0, nz(Vs), 32, Vt.data_ptr()), S, Sp)
-        else:
-            proj(k_in, E, (kx, 1.0, Ks.data_ptr(), QKW, nz(Kt)), None, S, Sp)
-            proj(v_in, 2 * E, (None, 1.0, nz(Vs), 32, Vt.data_ptr()), None, S, Sp)
-    return Qs, Ks, Vt, Lqp, Sp, scale, freq, (Qt, Kt, Vs)
 
 
 class DropCtx:
@@ -556,35 +654,23 @@ def attn_core_fwd(Qs, Ks, Vt, kmask, B, H, Lq, Lqp, S, Sp, nsplit, drop=None, si
     E = H * 15
     O = torch.empty((B, Lq, E), device=dev, dtype=F32)
     LSE = torch.empty((B, H, Lqp), device=dev, dtype=F32)
-    ws = None
-    if nsplit > 1:
-        ws = torch.empty((nsplit * B * H * Lqp * 18,), device=dev, dtype=F32)
-    if Qs.dtype == torch.float16:
-        dropping = drop is not None and drop.p > 0
-        if ATTN_MODE == "fp8" and not dropping and not need_bwd:
-            if Vt.dim() == 4:
-                raise RuntimeError("attn_core_fwd: the fp8 mode packs its value operand from value PLANES; these operands were built "
-                                   "in the rows-only set (build them with ops.ATTN_MODE == 'fp8')")
-            ops8 = torch.empty((L.load().a3d_attn8_operand_bytes(B, H, Sp),), device=dev, dtype=torch.uint8)
-            L.call("a3d_attn8_fwd", Qs.data_ptr(), Ks.data_ptr(), Vt.data_ptr(), ops8.data_ptr(),
-                   None if kmask is None else kmask.data_ptr(), O.data_ptr(), LSE.data_ptr(),
-                   None if ws is None else ws.data_ptr(), B, H, Lq, Lqp, S, Sp, nsplit, L.stream())
-            return O, LSE
+    ws = torch.empty((nsplit * B * H * Lqp * 18,), device=dev, dtype=F32) if nsplit > 1 else None
+    f16, dropping = Qs.dtype == torch.float16, drop is not None and drop.p > 0
+    entry = _core_fwd_entry(f16, Vt.dim() == 4, dropping, need_bwd)
+    args = [Qs.data_ptr(), Ks.data_ptr(), Vt.data_ptr(), None if kmask is None else kmask.data_ptr(), O.data_ptr(), LSE.data_ptr(),
+            None if ws is None else ws.data_ptr(), B, H, Lq, Lqp, S, Sp, nsplit]
+    if entry == "a3d_attn8_fwd":
         if Vt.dim() == 4:
-            L.call("a3d_attn16_fwd_rows", Qs.data_ptr(), Ks.data_ptr(), Vt.data_ptr(), None if kmask is None else kmask.data_ptr(),
-                   O.data_ptr(), LSE.data_ptr(), None if ws is None else ws.data_ptr(), B, H, Lq, Lqp, S, Sp, nsplit,
-                   drop.state.data_ptr() if dropping else None, int(site), drop.p if dropping else 0.0, 1 if nograd else 0, L.stream())
-            return O, LSE
-        L.call("a3d_attn16_fwd", Qs.data_ptr(), Ks.data_ptr(), Vt.data_ptr(), None if kmask is None else kmask.data_ptr(),
-               O.data_ptr(), LSE.data_ptr(), None if ws is None else ws.data_ptr(), B, H, Lq, Lqp, S, Sp, nsplit,
-               drop.state.data_ptr() if dropping else None, int(site), drop.p if dropping else 0.0, L.stream())
-        return O, LSE
-    args = (Qs.data_ptr(), Ks.data_ptr(), Vt.data_ptr(), None if kmask is None else kmask.data_ptr(),
-            O.data_ptr(), LSE.data_ptr(), None if ws is None else ws.data_ptr(), B, H, Lq, Lqp, S, Sp, nsplit)
-    if drop is not None and drop.p > 0:
-        L.call("a3d_attn_fwd_dropout", *args, drop.state.data_ptr(), int(site), drop.p, L.stream())
-    else:
-        L.call("a3d_attn_fwd", *args, L.stream())
+            raise RuntimeError("attn_core_fwd: the fp8 mode packs its value operand from value PLANES; these operands were built "
+                               "in the rows-only set (build them with ops.ATTN_MODE == 'fp8')")
+        ops8 = torch.empty((L.load().a3d_attn8_operand_bytes(B, H, Sp),), device=dev, dtype=torch.uint8)
+        args.insert(3, ops8.data_ptr())
+    elif f16:
+        args += [drop.state.data_ptr() if dropping else None, int(site), drop.p if dropping else 0.0]
+        args += [1 if nograd else 0] if entry == "a3d_attn16_fwd_rows" else []
+    elif dropping:
+        args += [drop.state.data_ptr(), int(site), drop.p]
+    L.call(entry, *args, L.stream())
     return O, LSE
 
 
@@ -603,7 +689,7 @@ def attn_core_bwd(Qs, Ks, Vt, kmask, O, dO, LSE, B, H, Lq, Lqp, S, Sp, nsplit, e
         dOr = torch.empty((B, H, Lqp, 32), device=dev, dtype=torch.float16)          # row-normalised dO ln2: hi | lo
         dOp = torch.empty((L.load().a3d_attn16_bwd_pack_bytes(B, H, Lqp) // 2,), device=dev, dtype=torch.float16)
         rexp = torch.empty((B, H, Lqp), device=dev, dtype=torch.int32)
-        L.call("a3d_attn16_bwd", Qs.data_ptr(), None, Ks.data_ptr(), None, Vr.data_ptr(), km, O.data_ptr(),
+        L.call(_core_bwd_entry(True, dropping), Qs.data_ptr(), None, Ks.data_ptr(), None, Vr.data_ptr(), km, O.data_ptr(),
                dO.data_ptr(), LSE.data_ptr(), dOr.data_ptr(), dOp.data_ptr(), D.data_ptr(), rexp.data_ptr(), dQp.data_ptr(),
                dK.data_ptr(), dV.data_ptr(), B, H, Lq, Lqp, S, Sp, nsplit, drop.state.data_ptr() if dropping else None,
                int(site), drop.p if dropping else 0.0, L.stream())
@@ -616,10 +702,7 @@ def attn_core_bwd(Qs, Ks, Vt, kmask, O, dO, LSE, B, H, Lq, Lqp, S, Sp, nsplit, e
     args = (Qs.data_ptr(), Qt.data_ptr(), Ks.data_ptr(), Kt.data_ptr(), Vs.data_ptr(), km,
             O.data_ptr(), dO.data_ptr(), LSE.data_ptr(), dOs.data_ptr(), dOt.data_ptr(), D.data_ptr(), dQp.data_ptr(),
             dK.data_ptr(), dV.data_ptr(), B, H, Lq, Lqp, S, Sp, nsplit)
-    if dropping:
-        L.call("a3d_attn_bwd_bf16_dropout", *args, drop.state.data_ptr(), int(site), drop.p, L.stream())
-    else:
-        L.call("a3d_attn_bwd_bf16", *args, L.stream())
+    L.call(_core_bwd_entry(False, dropping), *args, *((drop.state.data_ptr(), int(site), drop.p) if dropping else ()), L.stream())
     return dQp, dK, dV
 
 
@@ -798,8 +881,7 @@ class AttnBlockFn(torch.autograd.Function):
 
     Mirrors MultiheadCustomAttention.forward + the post-norm residual of RelativeCrossAttentionLayer
     (layers.py:299-310) and ParallelAttentionLayer (layers.py:139-159,176-191) in the reference.
-    ``mode``: "kv" (key is value: packed k,v projection -- multihead_custom_attention.py:251-275),
-              "qk" (query is key, value differs -- :277-303), "none" (three inputs).
+    ``mode``: a key of PROJ_GROUPS.  attn_block_plan names the launches; forward and backward dispatch on its route.
     Returns (y, attn_out) where attn_out is the pre-residual attention output (rarely needed).
     """
     @staticmethod
@@ -822,49 +904,15 @@ class AttnBlockFn(torch.autograd.Function):
             q_xyz, k_xyz = _c(q_xyz.to(F32)), _c(k_xyz.to(F32))
         if kmask is not None:
             kmask = _c(kmask.to(torch.uint8))
-        wp, bp = in_w.data_ptr(), in_b.data_ptr()
-        f4 = 4
         # whether a backward can follow: the in-projection parameters count (they get .grad through wgrad even when no
         # input needs a gradient); under torch.no_grad() none follows whatever the parameters say
         need_bwd = bool(grad_mode) and (any(ctx.needs_input_grad) or in_w.requires_grad)
-        if kv_pair is not None:
-            # ---- k | v rows written once for all layers of this context; only q is projected here
-            if mode != "kv":
-                raise RuntimeError("AttnBlockFn: precomputed context operands need the packed k,v projection (key is value)")
-            Qs, Ks, Vt, Lqp, Sp, scale, freq, extra = attn_operands_fused16(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S,
-                                                                            E, H, dev, need_bwd, kv_pair=kv_pair)
-        elif FUSED_PROJ and E % 4 == 0 and E <= 128:
-            # ---- projections fused with RoPE + operand formatting: the projected rows never reach HBM
-            fused = attn_operands_fused16 if _use16(Lq, need_bwd) else attn_operands_fused
-            Qs, Ks, Vt, Lqp, Sp, scale, freq, extra = fused(mode, q_in, k_in, v_in, wp, bp, q_xyz, k_xyz, B, Lq, S, E, H, dev,
-                                                            need_bwd)
-        else:
-            # ---- projections, then RoPE + operand formatting
-            if mode == "qk":
-                qk_pre = linear_raw(q_in.data_ptr(), E, wp, E, bp, B * Lq, 2 * E, E, dev)            # [B*Lq, 2E]
-                q_ptr, ldq = qk_pre.data_ptr(), 2 * E
-                k_ptr, ldk = qk_pre.data_ptr() + E * f4, 2 * E
-                v_pre = linear_raw(v_in.data_ptr(), E, wp + 2 * E * E * f4, E, bp + 2 * E * f4, B * S, E, E, dev)
-                v_ptr, ldv = v_pre.data_ptr(), E
-                keep = (qk_pre, v_pre)
-            else:
-                q_pre = linear_raw(q_in.data_ptr(), E, wp, E, bp, B * Lq, E, E, dev)
-                q_ptr, ldq = q_pre.data_ptr(), E
-                if mode == "kv":
-                    kv_pre = linear_raw(k_in.data_ptr(), E, wp + E * E * f4, E, bp + E * f4, B * S, 2 * E, E, dev)
-                    k_ptr, ldk = kv_pre.data_ptr(), 2 * E
-                    v_ptr, ldv = kv_pre.data_ptr() + E * f4, 2 * E
-                    keep = (q_pre, kv_pre)
-                else:
-                    k_pre = linear_raw(k_in.data_ptr(), E, wp + E * E * f4, E, bp + E * f4, B * S, E, E, dev)
-                    v_pre = linear_raw(v_in.data_ptr(), E, wp + 2 * E * E * f4, E, bp + 2 * E * f4, B * S, E, E, dev)
-                    k_ptr, ldk, v_ptr, ldv = k_pre.data_ptr(), E, v_pre.data_ptr(), E
-                    keep = (q_pre, k_pre, v_pre)
-            unfused = attn_operands16 if _use16(Lq, need_bwd) else attn_operands
-            Qs, Ks, Vt, Lqp, Sp, scale, freq, extra = unfused(q_ptr, ldq, k_ptr, ldk, v_ptr, ldv, q_xyz, k_xyz, B, Lq,
-                                                              S, E, H, dev, need_bwd=need_bwd)
-            del keep
-        nsplit = pick_nsplit(B, H, Lqp, Sp)
+        route = attn_block_plan(mode, B, Lq, S, E, H, need_bwd, drop is not None, kv_pair is not None,
+                                sink is not None and tuple(k_in.shape) == sink.shape, q_is_resid, ctx.needs_input_grad[:4])
+        Qs, Ks, Vt, Lqp, Sp, scale, freq, extra = _operands(route.f16, route.groups, (q_in, k_in, v_in), in_w.data_ptr(), in_b.data_ptr(),
+                                                            q_xyz, k_xyz, B, Lq, S, E, H, dev, need_bwd,
+                                                            fused=route.projection != "unfused", kv_pair=kv_pair)
+        nsplit = route.nsplit
         O, LSE = attn_core_fwd(Qs, Ks, Vt, kmask, B, H, Lq, Lqp, S, Sp, nsplit, drop=drop, site=site, need_bwd=need_bwd,
                                nograd=not need_bwd)
         Y = linear2d(O.view(B * Lq, E), out_w, out_b, drop=drop, site=site + 1)   # seq1 + dropout(attn_out): Y is the dropped branch
@@ -881,9 +929,7 @@ class AttnBlockFn(torch.autograd.Function):
         # the usual post-norm layer: the query IS the residual stream -- its two gradients are summed by the dgrad kernel (in place, into
         # the LayerNorm's input gradient) instead of by an autograd add
         ctx.q_is_resid = bool(q_is_resid)
-        # the context's gradient goes into its shared buffer (packed k,v projection of ONE input only: a single dgrad GEMM)
-        ctx.sink = sink if (sink is not None and need_bwd and mode == "kv" and ctx.needs_input_grad[1] and
-                            tuple(k_in.shape) == sink.shape) else None
+        ctx.sink = sink if route.sink else None
         if ctx.sink is not None:
             ctx.sink.expected += 1
         return y.view(B, Lq, E)
@@ -904,7 +950,6 @@ class AttnBlockFn(torch.autograd.Function):
             kmask = None
         freq = rope_freq(E, dev)
         dy = _c(dy).view(B * Lq, E)
-        f4 = 4
         if ctx.drop is None:
             dS = dYo = add_layernorm_bwd(resid.view(B * Lq, E), Y, ln_g, ln_b, mean, rstd, dy)     # = d resid = d Y
         else:                                                                                     # dYo: through the residual dropout
@@ -915,72 +960,43 @@ class AttnBlockFn(torch.autograd.Function):
                                     extra=ctx.extra, drop=ctx.drop, site=ctx.site)
         gW, gb = grad_buf(in_w), grad_buf(in_b)
         st = L.stream()
-        need_q, need_k, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        d_q_in = d_k_in = d_v_in = None
-        fold_q = ctx.q_is_resid and ctx.needs_input_grad[3]      # d_q_in is added into dS (no reader of dS / dYo is left by then)
-        if mode == "qk":
-            dqk = torch.empty((B * Lq, 2 * E), device=dev, dtype=F32)
-            rope_merge(dQp, nsplit, q_xyz, freq, scale, dqk.data_ptr(), 2 * E, B, Lq, Lqp, E, H)
-            rope_merge(dK, 1, k_xyz, freq, 1.0, dqk.data_ptr() + E * f4, 2 * E, B, S, Sp, E, H)
-            dv_pre = torch.empty((B * S, E), device=dev, dtype=F32)
-            rope_merge(dV, 1, None, freq, 1.0, dv_pre.data_ptr(), E, B, S, Sp, E, H)
-            wgrad_raw(dqk.data_ptr(), 2 * E, q_in.data_ptr(), E, gW.data_ptr(), E, gb.data_ptr(),
-                   B * Lq, 2 * E, E, dev, st)
-            wgrad_raw(dv_pre.data_ptr(), E, v_in.data_ptr(), E, gW.data_ptr() + 2 * E * E * f4, E,
-                   gb.data_ptr() + 2 * E * f4, B * S, E, E, dev, st)
-            if (need_q or need_k) and fold_q:
-                linear_raw(dqk.data_ptr(), 2 * E, in_w.data_ptr(), E, None, B * Lq, E, 2 * E, dev, act=3, transposed=True, out=dS)
-            elif need_q or need_k:
-                d_q_in = linear_raw(dqk.data_ptr(), 2 * E, in_w.data_ptr(), E, None, B * Lq, E, 2 * E, dev,
-                                    transposed=True).view(B, Lq, E)
-            if need_v:
-                d_v_in = linear_raw(dv_pre.data_ptr(), E, in_w.data_ptr() + 2 * E * E * f4, E, None, B * S, E, E, dev,
-                                    transposed=True).view(B, S, E)
-        else:
-            dq_pre = torch.empty((B * Lq, E), device=dev, dtype=F32)
-            rope_merge(dQp, nsplit, q_xyz, freq, scale, dq_pre.data_ptr(), E, B, Lq, Lqp, E, H)
-            wgrad_raw(dq_pre.data_ptr(), E, q_in.data_ptr(), E, gW.data_ptr(), E, gb.data_ptr(),
-                   B * Lq, E, E, dev, st)
-            if need_q and fold_q:
-                dgrad2d(dq_pre, in_w[:E], accum_into=dS)
-            elif need_q:
-                d_q_in = dgrad2d(dq_pre, in_w[:E]).view(B, Lq, E)
-            if mode == "kv" and ctx.sink is not None and CTX_DEFER:
-                # park dK | dV next to the other blocks' (GradSink, "deferred projection gradients"): the input- and the weight-
-                # gradient GEMMs of all blocks that read this context run once, at the gate
-                ptr, ld = ctx.sink.park(k_in, 2 * E)
-                rope_merge(dK, 1, k_xyz, freq, 1.0, ptr, ld, B, S, Sp, E, H)
-                rope_merge(dV, 1, None, freq, 1.0, ptr + E * f4, ld, B, S, Sp, E, H)
-                d_k_in = ctx.sink.parked_done(in_w[E:], gW[E:], gb[E:])
-            elif mode == "kv":
-                dkv = torch.empty((B * S, 2 * E), device=dev, dtype=F32)
-                rope_merge(dK, 1, k_xyz, freq, 1.0, dkv.data_ptr(), 2 * E, B, S, Sp, E, H)
-                rope_merge(dV, 1, None, freq, 1.0, dkv.data_ptr() + E * f4, 2 * E, B, S, Sp, E, H)
-                wgrad_raw(dkv.data_ptr(), 2 * E, k_in.data_ptr(), E, gW.data_ptr() + E * E * f4, E,
-                       gb.data_ptr() + E * f4, B * S, 2 * E, E, dev, st)
-                if ctx.sink is not None:
-                    buf, acc = ctx.sink.begin()
-                    linear_raw(dkv.data_ptr(), 2 * E, in_w.data_ptr() + E * E * f4, E, None, B * S, E, 2 * E, dev,
-                               act=3 if acc else 0, transposed=True, out=buf.view(B * S, E))
-                    d_k_in = ctx.sink.end()                  # None: the sink's gate node hands the total to autograd
-                elif need_k or need_v:
-                    d_k_in = linear_raw(dkv.data_ptr(), 2 * E, in_w.data_ptr() + E * E * f4, E, None, B * S, E, 2 * E,
-                                        dev, transposed=True).view(B, S, E)
+        needs = ctx.needs_input_grad
+        fold_q = ctx.q_is_resid and needs[3]                     # d_q_in is added into dS (no reader of dS / dYo is left by then)
+        x, d_in = (q_in, k_in, v_in), [None, None, None]
+        role = {"q": Role(q_xyz, scale, Lq, Lqp, dQp, nsplit), "k": Role(k_xyz, 1.0, S, Sp, dK), "v": Role(None, 1.0, S, Sp, dV)}
+        for src, w0, roles in PROJ_GROUPS[mode]:
+            w_off, b_off, cols, ld = group_layout(w0, roles, E)
+            N = role[roles[0]].n
+            to = _group_grad_route(roles, needs, ctx.sink is not None, fold_q)
+            if to == "parked":
+                # next to the other blocks' rows (GradSink, "deferred projection gradients"): the input- and the weight-gradient
+                # GEMMs of all blocks that read this context run once, at the gate
+                ptr, ldg = ctx.sink.park(x[src], ld)
             else:
-                dk_pre = torch.empty((B * S, E), device=dev, dtype=F32)
-                dv_pre = torch.empty((B * S, E), device=dev, dtype=F32)
-                rope_merge(dK, 1, k_xyz, freq, 1.0, dk_pre.data_ptr(), E, B, S, Sp, E, H)
-                rope_merge(dV, 1, None, freq, 1.0, dv_pre.data_ptr(), E, B, S, Sp, E, H)
-                wgrad_raw(dk_pre.data_ptr(), E, k_in.data_ptr(), E, gW.data_ptr() + E * E * f4, E,
-                       gb.data_ptr() + E * f4, B * S, E, E, dev, st)
-                wgrad_raw(dv_pre.data_ptr(), E, v_in.data_ptr(), E, gW.data_ptr() + 2 * E * E * f4,
-                       E, gb.data_ptr() + 2 * E * f4, B * S, E, E, dev, st)
-                if need_k:
-                    d_k_in = dgrad2d(dk_pre, in_w[E:2 * E]).view(B, S, E)
-                if need_v:
-                    d_v_in = dgrad2d(dv_pre, in_w[2 * E:]).view(B, S, E)
-        d_resid = dS.view(B, Lq, E) if ctx.needs_input_grad[3] else None
-        return (d_q_in, d_k_in, d_v_in, d_resid) + (None,) * 17
+                g = torch.empty((B * N, ld), device=dev, dtype=F32)
+                ptr, ldg = g.data_ptr(), ld
+            for r, c in zip(roles, cols):
+                ro = role[r]
+                rope_merge(ro.grad, ro.nsplit, ro.xyz, freq, ro.scale, ptr + c, ldg, B, ro.n, ro.npad, E, H)
+            if to == "parked":
+                blocks = slice(w0 * E, (w0 + len(roles)) * E)
+                d_in[src] = ctx.sink.parked_done(in_w[blocks], gW[blocks], gb[blocks])
+                continue
+            wgrad_raw(ptr, ld, x[src].data_ptr(), E, gW.data_ptr() + w_off, E, gb.data_ptr() + b_off, B * N, ld, E, dev, st)
+            if to is None:
+                continue
+            if to == "sink":
+                buf, acc = ctx.sink.begin()
+                out = buf.view(B * N, E)
+            else:
+                out, acc = (dS, True) if to == "fold" else (None, False)
+            d = linear_raw(ptr, ld, in_w.data_ptr() + w_off, E, None, B * N, E, ld, dev, act=3 if acc else 0, transposed=True, out=out)
+            if to == "sink":
+                d_in[src] = ctx.sink.end()                       # None: the sink's gate node hands the total to autograd
+            elif to == "fresh":
+                d_in[src] = d.view(B, N, E)
+        d_resid = dS.view(B, Lq, E) if needs[3] else None
+        return (*d_in, d_resid) + (None,) * 17
 
 
 SINGLE_QUERY = os.environ.get("A3D_SINGLE_QUERY", "1") == "1"
@@ -1803,29 +1819,16 @@ def ddpm_step_sched(model_out, sample, noise, cond_data, cond_mask_u8, coef_pos,
 
 
 # ------------------------------------------------------------------------------------------------ inference K/V cache
+# The (k, v) group and the q group of mode "kv" in the bf16 family, forward only: the cache holds K rows and V planes, the query rows only.
 def kv_cache_build(k_in, k_xyz, mha, H):
     """Step-invariant K/V operands of one cross-attention layer (context projected, rotated, split) -- computed once per
     trajectory batch instead of once per denoise step (SURVEY §0 "re-encodes ... every step", §8f-2)."""
     k_in = _c(k_in)
     B, S, E = k_in.shape
-    dev = k_in.device
-    f4 = 4
-    Sp = ceil_to(S, 64)
-    freq = rope_freq(E, dev)
-    Ks = torch.empty((B, H, Sp, QKW), device=dev, dtype=torch.bfloat16)
-    Vt = torch.empty((B, H, 2, 16, Sp), device=dev, dtype=torch.bfloat16)
-    st = L.stream()
-    k_xyz = None if k_xyz is None else _c(k_xyz.to(F32))      # keep the (possibly converted) tensor alive
-    kx = None if k_xyz is None else k_xyz.data_ptr()
-    if FUSED_PROJ and E % 4 == 0 and E <= 128:
-        L.call("a3d_proj_rope_split", k_in.data_ptr(), E, mha.in_proj_weight.data_ptr() + E * E * f4, E,
-               mha.in_proj_bias.data_ptr() + E * f4, E, kx, 1.0, Ks.data_ptr(), QKW, None, None, 1.0, None, 32, Vt.data_ptr(),
-               freq.data_ptr(), B, S, Sp, E, H, st)
-    else:
-        kv_pre = linear_raw(k_in.data_ptr(), E, mha.in_proj_weight.data_ptr() + E * E * f4, E,
-                            mha.in_proj_bias.data_ptr() + E * f4, B * S, 2 * E, E, dev)
-        L.call("a3d_rope_split_qk", kv_pre.data_ptr(), 2 * E, kx, freq.data_ptr(), 1.0, Ks.data_ptr(), B, S, Sp, E, H, st)
-        L.call("a3d_split_vt", kv_pre.data_ptr() + E * f4, 2 * E, Vt.data_ptr(), B, S, Sp, E, H, st)
+    k_xyz = None if k_xyz is None else _c(k_xyz.to(F32))
+    _, Ks, Vt, _, Sp, _, _, _ = _operands(False, PROJ_GROUPS["kv"][1:], (None, k_in, k_in), mha.in_proj_weight.data_ptr(),
+                                          mha.in_proj_bias.data_ptr(), None, k_xyz, B, S, S, E, H, k_in.device, False,
+                                          fused=_fused_proj(E))
     return {"Ks": Ks, "Vt": Vt, "S": S, "Sp": Sp}
 
 
@@ -1834,20 +1837,10 @@ def attn_block_cached(q_in, resid, q_xyz, cache, mha, norm, H):
     """Inference-only cross-attention block against a prebuilt K/V cache: q-proj + RoPE + attention + out-proj + add&LN."""
     q_in, resid = _c(q_in), _c(resid)
     B, Lq, E = q_in.shape
-    dev = q_in.device
-    Lqp = ceil_to(Lq, 64)
-    Qs = torch.empty((B, H, Lqp, QKW), device=dev, dtype=torch.bfloat16)
-    freq = rope_freq(E, dev)
-    q_xyz = None if q_xyz is None else _c(q_xyz.to(F32))      # keep the (possibly converted) tensor alive
-    qx = None if q_xyz is None else q_xyz.data_ptr()
-    if FUSED_PROJ and E % 4 == 0 and E <= 128:
-        L.call("a3d_proj_rope_split", q_in.data_ptr(), E, mha.in_proj_weight.data_ptr(), E, mha.in_proj_bias.data_ptr(), E,
-               qx, float(E // H) ** -0.5, Qs.data_ptr(), QKW, None, None, 1.0, None, 32, None, freq.data_ptr(), B, Lq, Lqp, E,
-               H, L.stream())
-    else:
-        q_pre = linear_raw(q_in.data_ptr(), E, mha.in_proj_weight.data_ptr(), E, mha.in_proj_bias.data_ptr(), B * Lq, E, E, dev)
-        L.call("a3d_rope_split_qk", q_pre.data_ptr(), E, qx, freq.data_ptr(), float(E // H) ** -0.5, Qs.data_ptr(), B, Lq, Lqp,
-               E, H, L.stream())
+    q_xyz = None if q_xyz is None else _c(q_xyz.to(F32))
+    Qs, _, _, Lqp, _, _, _, _ = _operands(False, PROJ_GROUPS["kv"][:1], (q_in, None, None), mha.in_proj_weight.data_ptr(),
+                                          mha.in_proj_bias.data_ptr(), q_xyz, None, B, Lq, cache["S"], E, H, q_in.device, False,
+                                          fused=_fused_proj(E))
     nsplit = pick_nsplit(B, H, Lqp, cache["Sp"])
     O_, _ = attn_core_fwd(Qs, cache["Ks"], cache["Vt"], None, B, H, Lq, Lqp, cache["S"], cache["Sp"], nsplit)
     Y = linear2d(O_.view(B * Lq, E), mha.out_proj.weight, mha.out_proj.bias)
