@@ -8,6 +8,8 @@ TrainTester.train_one_step (main_keypose.py:207-234, main_trajectory.py:177-204)
   save/load_checkpoint -> {"weight" (module.-prefixed), "optimizer", "iter", "best_loss"}
 The reference's CLI, data loaders, tensorboard and evaluation loop are out of scope.
 """
+import contextlib
+import math
 import os
 
 import torch
@@ -90,11 +92,34 @@ class FlatParams:
                 break
 
 
-class FlatAdamW:
-    """torch.optim.AdamW semantics (lr, betas, eps, two weight-decay groups) as one fused kernel over FlatParams."""
+def _check_ema(ema_decay, ema_warmup):
+    """The ranges a3d_adamw_ema_step accepts, checked where the keywords enter.  Returns (decay or None, warmup) as floats."""
+    if ema_decay is None:
+        return None, float(ema_warmup)
+    d, w = float(ema_decay), float(ema_warmup)
+    if not (math.isfinite(d) and 0.0 <= d < 1.0):
+        raise ValueError("ema_decay = %r is outside [0, 1)" % (ema_decay,))
+    if not (w == 0.0 or (math.isfinite(w) and w >= 1.0)):
+        raise ValueError("ema_warmup = %r must be 0 (constant decay) or a finite value >= 1" % (ema_warmup,))
+    return d, w
 
-    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4):
+
+class FlatAdamW:
+    """torch.optim.AdamW semantics (lr, betas, eps, two weight-decay groups) as one fused kernel over FlatParams.
+
+    With `ema_decay` the same launch also keeps an exponential moving average of the weights (`ema`, a second flat buffer;
+    DESIGN 4.21): decay min(ema_decay, (1 + t) / (ema_warmup + t)) at the t-th EMA update, t counted on the device
+    (`ema_updates`).  The averages are read by exchanging them with the weights IN PLACE (`swap_ema`, `ema_weights()`): the
+    parameters are views of flat.flat and every captured graph addresses that buffer, so nothing is rebound."""
+
+    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4, ema_decay=None, ema_warmup=10):
         self.flat, self.betas, self.eps, self.weight_decay = flat, betas, eps, weight_decay
+        self.ema_decay, self.ema_warmup = _check_ema(ema_decay, ema_warmup)
+        self.ema = self.ema_state = None
+        self.ema_swapped = False                 # True while flat.flat holds the averages and `ema` the raw weights
+        if self.ema_decay is not None:
+            self.ema = flat.flat.detach().clone()
+            self.ema_state = torch.zeros(4, device=flat.flat.device, dtype=torch.float32)       # {w, updates, 0, 0}
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
         self.step_count = torch.zeros(1, device=flat.flat.device, dtype=torch.float32)     # optimizer.step() calls so far
@@ -121,6 +146,16 @@ class FlatAdamW:
 
     def step(self, grad_scale=1.0):
         f = self.flat
+        if self.ema is not None:
+            if self.ema_swapped:
+                raise RuntimeError("FlatAdamW.step() while the EMA weights are swapped in: it would train the averages "
+                                   "(leave ema_weights() / call swap_ema() first)")
+            L.call("a3d_adamw_ema_step", f.flat.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
+                   self.exp_avg_sq.data_ptr(), self.ema.data_ptr(), self.step_count.data_ptr(), self.seg_off.data_ptr(),
+                   self.seg_state.data_ptr(), self.ema_state.data_ptr(), len(f.order), f.n, f.n_nodecay, float(self.lr),
+                   self.betas[0], self.betas[1], self.eps, 0.0, float(self.weight_decay), float(grad_scale),
+                   self.ema_decay, self.ema_warmup, L.stream())
+            return
         L.call("a3d_adamw_step", f.flat.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
                self.exp_avg_sq.data_ptr(), self.step_count.data_ptr(), self.seg_off.data_ptr(), self.seg_state.data_ptr(),
                len(f.order), f.n, f.n_nodecay, float(self.lr),
@@ -134,6 +169,52 @@ class FlatAdamW:
     def reset_state(self):
         """Fresh-optimizer state: zero moments and step counts (parameters re-join with their first gradient)."""
         self.exp_avg.zero_(); self.exp_avg_sq.zero_(); self.step_count.zero_(); self.seg_state.zero_()
+        if self.ema is not None:
+            self.reset_ema()
+
+    # ---- EMA of the weights (ema_decay is not None)
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError("%s: this optimizer keeps no EMA (built with ema_decay=None)" % what)
+
+    @property
+    def ema_updates(self):
+        """EMA updates so far: a view of the device counter the kernel advances (ema_state[1])."""
+        self._need_ema("ema_updates")
+        return self.ema_state[1]
+
+    def reset_ema(self):
+        """Restart the average from the current weights; the warm-up starts over."""
+        self._need_ema("reset_ema")
+        if self.ema_swapped:
+            raise RuntimeError("reset_ema() while the EMA weights are swapped in")
+        self.ema.copy_(self.flat.flat.detach())
+        self.ema_state.zero_()
+
+    def swap_ema(self):
+        """Exchange weights and averages in place (stream-ordered, one pass); call again to swap back."""
+        self._need_ema("swap_ema")
+        L.call("a3d_swap_f32", self.flat.flat.data_ptr(), self.ema.data_ptr(), self.flat.n, L.stream())
+        self.ema_swapped = not self.ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with optimizer.ema_weights():` the model computes with the averaged weights; without an EMA a no-op."""
+        if self.ema is None:
+            yield
+            return
+        self.swap_ema()
+        try:
+            yield
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self):
+        """{parameter name: averaged values} for the parameters of the flat buffer (detached clones, parameter shapes),
+        wherever the averages currently live (`ema`, or flat.flat while swapped in)."""
+        self._need_ema("ema_state_dict")
+        src = self.flat.flat if self.ema_swapped else self.ema
+        return {n: src[slice(*self.flat.slices[n])].detach().clone().view(p.shape) for n, p in self.flat.order}
 
     def state_dict(self):
         """torch.optim.AdamW's state_dict layout for the reference's optimizer (engine.py:89-102: two groups over ALL named
@@ -196,12 +277,14 @@ class FlatAdamW:
         self.lr = sd["param_groups"][0].get("lr", self.lr)
 
 
-def get_optimizer(model, lr=1e-4, active_names=None):
+def get_optimizer(model, lr=1e-4, active_names=None, ema_decay=None, ema_warmup=10):
     """engine.py:89-102 on the flat buffers.  Returns (FlatParams, FlatAdamW).  With active_names=None every trainable
     parameter is placed in the buffer; parameters that never receive a gradient are left untouched by the fused AdamW kernel
-    (as torch.optim.AdamW skips parameters whose .grad is None -- no weight decay on unused FPN blocks)."""
+    (as torch.optim.AdamW skips parameters whose .grad is None -- no weight decay on unused FPN blocks).  ema_decay / ema_warmup:
+    FlatAdamW's EMA of the weights (off by default)."""
+    _check_ema(ema_decay, ema_warmup)                # before the parameters are re-homed
     flat = FlatParams(model, active_names)
-    return flat, FlatAdamW(flat, lr=lr)
+    return flat, FlatAdamW(flat, lr=lr, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
 
 DP_ONESHOT = os.environ.get("A3D_DP_ONESHOT", "0") == "1"
@@ -444,25 +527,68 @@ class JointStep:
 
 def save_checkpoint(path, model, optimizer, step_id, best_loss=None):
     """engine.py:214-230 format: {"weight" (DDP's "module." prefix), "optimizer" (torch.optim.AdamW layout), "iter",
-    "best_loss"} -- loadable by the reference's load_checkpoint (engine.py:195-212)."""
+    "best_loss"} -- loadable by the reference's load_checkpoint (engine.py:195-212).  An optimizer that keeps an EMA adds a
+    fifth key the reference's loader never reads: "ema": {"weight" (same prefix, the flat buffer's parameters), "decay",
+    "warmup", "updates"}."""
+    ema = getattr(optimizer, "ema", None)
+    if ema is not None and optimizer.ema_swapped:
+        raise RuntimeError("save_checkpoint while the EMA weights are swapped in: \"weight\" would hold the averages")
     weight = {"module." + k: v.detach().clone() for k, v in model.state_dict().items()}
-    torch.save({"weight": weight, "optimizer": optimizer.state_dict(), "iter": step_id + 1, "best_loss": best_loss}, path)
+    d = {"weight": weight, "optimizer": optimizer.state_dict(), "iter": step_id + 1, "best_loss": best_loss}
+    if ema is not None:
+        d["ema"] = {"weight": {"module." + k: v.cpu() for k, v in optimizer.ema_state_dict().items()},
+                    "decay": optimizer.ema_decay, "warmup": optimizer.ema_warmup, "updates": int(optimizer.ema_updates.item())}
+    torch.save(d, path)
 
 
-def load_checkpoint(path, model, optimizer=None, strict=True):
+def _ema_entries(path, d):
+    if "ema" not in d:
+        raise RuntimeError("checkpoint %s holds no \"ema\" entry (it was written without ema_decay)" % path)
+    return {(k[7:] if k.startswith("module.") else k): v for k, v in d["ema"]["weight"].items()}
+
+
+def load_checkpoint(path, model, optimizer=None, strict=True, weights="raw"):
     """engine.py:195-212 (+ online_evaluation/eval1.py:138-152 prefix stripping).  Returns (start_iter, best_loss).
     strict (the reference's load_state_dict default): missing / unexpected weight keys raise.  Parameters keep their
-    storage (the flat buffer views): values are copied in place."""
+    storage (the flat buffer views): values are copied in place.
+    weights="ema" (deployment / evaluation, no optimizer): the trained parameters are then overwritten with the checkpoint's
+    averages.  An optimizer that keeps an EMA resumes it from the file's "ema" entry, or restarts it from the loaded weights when
+    the file has none."""
+    if weights not in ("raw", "ema"):
+        raise ValueError("load_checkpoint: weights=%r (expected \"raw\" or \"ema\")" % (weights,))
+    if weights == "ema" and optimizer is not None:
+        raise ValueError("load_checkpoint: weights=\"ema\" with an optimizer -- a resumed run starts from the raw weights")
     d = torch.load(path, map_location="cpu", weights_only=False)
     weight = {(k[7:] if k.startswith("module.") else k): v for k, v in d["weight"].items()}
     res = model.load_state_dict(weight, strict=False)
     if strict and (res.missing_keys or res.unexpected_keys):
         raise RuntimeError("checkpoint %s does not match the model: missing %s, unexpected %s" %
                            (path, res.missing_keys[:5], res.unexpected_keys[:5]))
+    if weights == "ema":
+        params = dict(model.named_parameters())
+        with torch.no_grad():
+            for n, v in _ema_entries(path, d).items():
+                if n not in params or params[n].numel() != v.numel():
+                    raise RuntimeError("checkpoint %s: EMA entry %s does not match a parameter of the model" % (path, n))
+                params[n].copy_(v.view(params[n].shape))
     if optimizer is not None:
         if "optimizer" not in d:
             raise RuntimeError("checkpoint %s holds no optimizer state" % path)
         optimizer.load_state_dict(d["optimizer"])
+        if getattr(optimizer, "ema", None) is not None:
+            if "ema" in d:
+                entries, f = _ema_entries(path, d), optimizer.flat
+                bad = [n for n in set(entries) | set(f.slices)
+                       if n not in entries or n not in f.slices or entries[n].numel() != f.slices[n][1] - f.slices[n][0]]
+                if bad:
+                    raise RuntimeError("checkpoint %s: EMA entries do not match the optimizer's parameters: %s" % (path, sorted(bad)[:5]))
+                for n, v in entries.items():
+                    optimizer.ema[slice(*f.slices[n])].copy_(v.reshape(-1))
+                optimizer.ema_state.zero_()
+                optimizer.ema_state[1] = float(d["ema"]["updates"])
+            else:
+                optimizer.reset_ema()
+                print("checkpoint %s holds no EMA: the average restarts from the loaded weights" % path)
     return d.get("iter", 0), d.get("best_loss", None)
 
 

@@ -159,6 +159,9 @@ SIGNATURES = {
     "a3d_philox4x32_10_host": (None, [_p, _p, _p]),
     "a3d_sincos_host": (None, [_p, _p, _p, _z]),
     "a3d_adamw_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _z, _z, _f, _f, _f, _f, _f, _f, _f, _p]),
+    # optim.hip
+    "a3d_adamw_ema_step": (_i, [_p] * 9 + [_i, _z, _z] + [_f] * 9 + [_p]),
+    "a3d_swap_f32": (_i, [_p, _p, _z, _p]),
     "a3d_dbg_mfma_bf16": (_i, [_p, _p, _p, _p]),
     "a3d_dbg_mfma_f32": (_i, [_p, _p, _p, _p]),
     "a3d_dbg_cvt_pk_bf16": (_i, [_p, _p, _i, _p]),

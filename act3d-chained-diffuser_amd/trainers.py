@@ -13,6 +13,7 @@ with the reference's `Arguments` fields.  The machinery underneath is this packa
   _Schedule    the iteration plan (what happens after step i) as data instead of inline modulo tests.
 Batches arrive through `data.DeviceLoader` (pinned copies + the GPU Resize augmentation one batch ahead).
 """
+import contextlib
 import json
 import os
 import pickle
@@ -276,16 +277,25 @@ class BaseTrainTester:
 
     def get_optimizer(self, model):
         """The reference's two AdamW groups (engine.py:89-102) as ONE fused optimizer over flat buffers (`optimizer.flat`)."""
-        return E.get_optimizer(model, lr=self.args.lr)[1]
+        return E.get_optimizer(model, lr=self.args.lr, ema_decay=getattr(self.args, "ema_decay", None) or None,
+                               ema_warmup=getattr(self.args, "ema_warmup", 10))[1]
+
+    def _eval_weights(self, optimizer):
+        """The weights an evaluation reads: the optimizer's EMA (swapped in for the duration) with args.ema_eval (default 1)
+        when there is one, else the raw weights."""
+        if optimizer is not None and getattr(optimizer, "ema", None) is not None and bool(getattr(self.args, "ema_eval", 1)):
+            return optimizer.ema_weights()
+        return contextlib.nullcontext()
 
     def _val_iters(self):
         return max(5, int(4 * len(self.args.tasks) / self.args.batch_size_val))
 
-    def _evaluation_round(self, model, criterion, train_loader, test_loader, step_id):
-        model.eval()
-        self.evaluate_nsteps(model, criterion, train_loader, step_id, val_iters=self._val_iters(), split='train')
-        model.eval()
-        new_loss = self.evaluate_nsteps(model, criterion, test_loader, step_id, val_iters=self._val_iters())
+    def _evaluation_round(self, model, criterion, train_loader, test_loader, step_id, optimizer=None):
+        with self._eval_weights(optimizer):
+            model.eval()
+            self.evaluate_nsteps(model, criterion, train_loader, step_id, val_iters=self._val_iters(), split='train')
+            model.eval()
+            new_loss = self.evaluate_nsteps(model, criterion, test_loader, step_id, val_iters=self._val_iters())
         model.train()
         return new_loss
 
@@ -297,6 +307,8 @@ class BaseTrainTester:
         if get_world_size() > 1:
             self.ddp = E.FlatDataParallel(optimizer.flat, overlap=True, model=model)
             self.ddp.broadcast_parameters()
+        if getattr(optimizer, "ema", None) is not None:
+            optimizer.reset_ema()            # the optimizer was built before the broadcast: average from rank 0's weights
         start, best_loss = 0, None
         if getattr(self.args, "checkpoint", None):
             if not os.path.isfile(self.args.checkpoint):
@@ -304,7 +316,8 @@ class BaseTrainTester:
             start, best_loss = self.load_checkpoint(model, optimizer)
         if bool(getattr(self.args, "eval_only", 0)):
             model.eval()
-            self.evaluate_nsteps(model, criterion, test_loader, step_id=-1, val_iters=self._val_iters())
+            with self._eval_weights(optimizer):
+                self.evaluate_nsteps(model, criterion, test_loader, step_id=-1, val_iters=self._val_iters())
             return model
         plan = _Schedule(start, self.args.train_iters, self.args.val_freq)
         batches = _cycle(train_loader)
@@ -312,7 +325,7 @@ class BaseTrainTester:
         for step_id in plan.steps():
             self.train_one_step(model, criterion, optimizer, step_id, next(batches))
             if plan.evaluates_after(step_id):
-                new_loss = self._evaluation_round(model, criterion, train_loader, test_loader, step_id)
+                new_loss = self._evaluation_round(model, criterion, train_loader, test_loader, step_id, optimizer=optimizer)
                 if get_rank() == 0:
                     best_loss = self.save_checkpoint(model, optimizer, step_id, new_loss, best_loss)
         return model

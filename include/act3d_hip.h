@@ -368,6 +368,21 @@ void a3d_sincos_host(const float* x, float* sn, float* cs, size_t n);
 int a3d_adamw_step(float* p, const float* g, float* m, float* v, float* step, const long long* seg_off, float* seg_state,
                    int nseg, size_t n, size_t n_nodecay, float lr, float beta1, float beta2, float eps, float wd_nodecay,
                    float wd_decay, float grad_scale, void* stream);
+/* a3d_adamw_step that also maintains an exponential moving average of the weights (csrc/optim.hip).  The reference has no EMA;
+ * this replaces a3d_adamw_step followed by torch's `ema.lerp_(p, w)` (one more launch, 10 instead of 9 floats moved per element,
+ * and a decay weight that would have to come from the host).  p, m, v, step and seg_state end bit for bit what a3d_adamw_step
+ * leaves.  ema [n] is updated as ema += w (p_new - ema) for the elements of the parameters that are active this step and left
+ * alone elsewhere.  ema_state [4] = {w, updates, 0, 0} lives on the device (zero-initialised by the caller): each call sets
+ * t = updates + 1, updates = t and w = max(1 - ema_decay, (ema_warmup - 1) / (ema_warmup + t)), i.e. the decay
+ * min(ema_decay, (1 + t) / (ema_warmup + t)); ema_warmup == 0 gives the constant w = 1 - ema_decay.  t counts EMA updates, not
+ * optimizer steps.  -22 for a null pointer, nseg <= 0, ema_decay outside [0, 1) or ema_warmup not 0 and not a finite value >= 1. */
+int a3d_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, float* step, const long long* seg_off,
+                       float* seg_state, float* ema_state, int nseg, size_t n, size_t n_nodecay, float lr, float beta1, float beta2,
+                       float eps, float wd_nodecay, float wd_decay, float grad_scale, float ema_decay, float ema_warmup,
+                       void* stream);
+/* a[i] <-> b[i] for i < n in one pass (csrc/optim.hip); replaces torch's three-copy exchange through a temporary (tmp = a.clone();
+ * a.copy_(b); b.copy_(tmp)).  Any n, pointers only 4-byte aligned.  -22 for a null pointer with n > 0 or overlapping ranges. */
+int a3d_swap_f32(float* a, float* b, size_t n, void* stream);
 
 /* ---- Act3D query stream, fused per layer (csrc/query_stream.hip; act3d.py:467-480, layers.py:293-351) -------------------------
  * One RelativeCrossAttentionLayer + FeedforwardLayer of the ONE-query-per-sample stream as four launches around a3d_sq_attn_fwd /
