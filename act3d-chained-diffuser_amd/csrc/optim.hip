@@ -1,33 +1,122 @@
-// Optimizer-side kernels on the flat parameter buffer (engine.FlatParams): the fused AdamW step that also maintains an exponential
-// moving average (EMA) of the weights, and the in-place exchange that lets evaluation / sampling / deployment read the averages
-// through the SAME storage every captured graph and pointer table already addresses.
+// Optimizer-side kernels on the flat parameter buffer (engine.FlatParams): the fused AdamW step, optionally with an exponential
+// moving average (EMA) of the weights and with global gradient-norm clipping, and the in-place exchange that lets evaluation /
+// sampling / deployment read the averages through the SAME storage every captured graph and pointer table already addresses.
 //
-//   a3d_adamw_ema_step : a3d_adamw_step (heads.hip: the same two launches, the same expression sequence) + per element
-//                            ema <- ema + w (p_new - ema)
-//                        for the elements of parameters that are active this step.  w lives on the device (ema_state[0]) and is
-//                        advanced by the prepare launch from the EMA's own update count (ema_state[1]): the warm-up needs no host
-//                        sync and nothing step-dependent is frozen into a captured graph.
-//   a3d_swap_f32       : a <-> b in one pass.
+//   a3d_adamw_step      : torch.optim.AdamW update on the flat parameter buffer (engine.py:89-102): prepare + update launch.
+//   a3d_adamw_ema_step  : the same two launches + per element
+//                             ema <- ema + w (p_new - ema)
+//                         for the elements of parameters that are active this step.  w lives on the device (ema_state[0]) and is
+//                         advanced by the prepare launch from the EMA's own update count (ema_state[1]): the warm-up needs no host
+//                         sync and nothing step-dependent is frozen into a captured graph.
+//   a3d_adamw_clip_step : a norm launch in front of the same two: sum g^2 in double -> one partial per workgroup; the prepare launch
+//                         combines the partials, decides {skip, clip coefficient} on the device and leaves the effective gradient
+//                         scale in clip_state[0], which the update launch reads in place of the host's grad_scale.  EMA optional.
+//   a3d_swap_f32        : a <-> b in one pass.
 #include "a3d_common.h"
 #include "../../include/act3d_hip.h"
 #include <algorithm>
 
 namespace a3d {
 
-// The two kernels below are heads.hip's adamw_prepare_kernel / adamw_kernel statement for statement (the per-parameter table, the
-// skip rule and the update are described there), with the EMA lines added: a3d_adamw_ema_step must leave p, m, v, step and seg_state
-// bit for bit as a3d_adamw_step does (tests/test_ema_gpu.py compares the two entries after every step).  A change to the
-// arithmetic of one is a change to both.
+// torch.optim.AdamW decides PER PARAMETER: a parameter whose .grad is None is skipped (no decay, no moment update, its own
+// `step` does not advance -- engine.py:121-124 find_unused_parameters: the FPN blocks / embeddings a configuration never
+// reads), every other parameter is updated in full, zero-gradient elements (dead ReLU rows, pad channels) included, with the
+// bias correction of ITS OWN step count.  The flat buffer has no None: seg_off [nseg + 1] delimits the parameters, and
+// seg_state [nseg][4] = {step, active, lr / bc1, sqrt(bc2)} carries the per-parameter state.  A parameter is "in the graph"
+// from the first step in which any element of its gradient segment is non-zero, and stays in (which tensors a model's
+// forward reaches is structural); adamw_prepare_kernel (one workgroup per parameter; the scan only runs until the parameter
+// is in) advances the step counts and leaves the coefficients for adamw_kernel, whose threads find their element's parameter
+// by bisection of the LDS-staged offsets.  Elements [0, n_nodecay) use weight decay wd0, the rest wd1.
+//
+// ONE prepare kernel and ONE update kernel serve the three entries: <EMA, CLIP> only add statements (if constexpr), so the
+// arithmetic of p, m, v, step and seg_state is the same expression sequence everywhere -- a3d_adamw_ema_step leaves them bit for bit
+// as a3d_adamw_step does, and a3d_adamw_clip_step as either of them called with grad_scale = clip_state[0] (tests/test_ema_gpu.py,
+// tests/test_grad_clip_gpu.py compare the entries after every step).
 constexpr int ADAMW_LDS_SEGS = 4096;
+constexpr int CLIP_PARTS = A3D_ADAMW_CLIP_WS_DOUBLES;       // workgroups of the norm pass = partials in clip_ws
+static_assert(CLIP_PARTS == 256, "clip_decide reads one partial per thread of a 256-thread workgroup");
+
+// Sum of one double per thread over a 256-thread workgroup, returned to EVERY thread with the same bits: an xor butterfly inside
+// the wave (lane i adds x[i ^ k], its partner the same two numbers the other way round: a + b == b + a), the four wave sums
+// through LDS, added in one fixed order.  No atomics, so the result depends on the inputs only.
+__device__ __forceinline__ double block_sum_f64(double x, double* wsum) {
+#pragma unroll
+  for (int k = 32; k >= 1; k >>= 1) x += __shfl_xor(x, k, 64);
+  __syncthreads();                             // wsum may still be read from a previous call
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// Norm pass: partial[blockIdx.x] = sum over this workgroup's grid-stride share of g[i]^2, squares and sums in double (the square of
+// an fp32 value is exact in double, and the sum of n < 2^64 of them cannot overflow).  The middle of g goes as float4 (g + head is
+// 16-byte aligned), the `head` < 4 leading and the < 4 trailing elements as scalars, as swap_f32_kernel does it.
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, size_t n, size_t head, size_t nvec,
+                                                          double* __restrict__ partial) {
+  __shared__ double wsum[4];
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+  const f32x4* gv = reinterpret_cast<const f32x4*>(g + head);
+  double acc = 0.0;
+  for (size_t i = tid; i < nvec; i += nthr) {
+    const f32x4 x = gv[i];
+    const double a = x[0], b = x[1], c = x[2], d = x[3];
+    acc += (a * a + b * b) + (c * c + d * d);
+  }
+  const size_t tail = head + nvec * 4;        // scalar elements: [0, head) and [tail, n)
+  for (size_t i = tid; i < head + (n - tail); i += nthr) {
+    const double a = g[i < head ? i : tail + (i - head)];
+    acc += a * a;
+  }
+  const double s = block_sum_f64(acc, wsum);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// The decision of a clipped step, derived by every workgroup that needs it from the same `nparts` partials with the same code,
+// hence with the same bits: norm = fp32(|gscale| sqrt(sum)), coef = min(1, max_norm / (norm + 1e-6)) (torch's clip_grad_norm_),
+// e = gscale * coef; a non-finite norm (a NaN / inf gradient element, or an fp32 overflow of the norm) skips the step.
+struct ClipDecision {
+  float e, norm, coef;
+  bool skip;
+};
+__device__ __forceinline__ ClipDecision clip_decide(const double* __restrict__ partial, int nparts, float gscale, float max_norm,
+                                                    double* wsum) {
+  const double sum = block_sum_f64((int)threadIdx.x < nparts ? partial[threadIdx.x] : 0.0, wsum);
+  ClipDecision d;
+  d.norm = (float)(fabs((double)gscale) * sqrt(sum));
+  d.skip = !isfinite(d.norm);
+  d.coef = d.skip ? 0.0f : fminf(1.0f, max_norm / (d.norm + 1e-6f));
+  d.e = d.skip ? 0.0f : gscale * d.coef;
+  return d;
+}
 
 // One workgroup per parameter; the thread that counts the optimizer step also advances the EMA:
 //   t = updates + 1;  w = 1 - min(decay, (1 + t) / (warmup + t)) = max(1 - decay, (warmup - 1) / (warmup + t))      (warmup >= 1)
 //   w = 1 - decay                                                                                                   (warmup == 0)
-__global__ __launch_bounds__(256) void adamw_ema_prepare_kernel(const float* __restrict__ g, const long long* __restrict__ seg_off,
-                                                                float* __restrict__ seg_state, float* __restrict__ step,
-                                                                float* __restrict__ ema_state, float lr, float beta1, float beta2,
-                                                                float ema_decay, float ema_warmup) {
+// CLIP: every workgroup first derives the decision; workgroup 0 records it in clip_state (the only writer, and nobody reads
+// clip_state in this launch), and on a skip every workgroup leaves before it has written anything.
+template <bool EMA, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_prepare_kernel(const float* __restrict__ g, const long long* __restrict__ seg_off,
+                                                            float* __restrict__ seg_state, float* __restrict__ step,
+                                                            float* __restrict__ ema_state, float* __restrict__ clip_state,
+                                                            const double* __restrict__ clip_ws, int clip_parts, float lr, float beta1,
+                                                            float beta2, float ema_decay, float ema_warmup, float gscale,
+                                                            float max_norm) {
   const int seg = blockIdx.x;
+  if constexpr (CLIP) {
+    __shared__ double wsum[4];
+    const ClipDecision d = clip_decide(clip_ws, clip_parts, gscale, max_norm, wsum);
+    if (seg == 0 && threadIdx.x == 0) {
+      clip_state[0] = d.e;
+      clip_state[1] = d.norm;
+      clip_state[2] = d.coef;
+      if (!d.skip && d.coef < 1.0f) clip_state[3] += 1.0f;
+      if (d.skip) clip_state[4] += 1.0f;
+      clip_state[5] = d.skip ? 1.0f : 0.0f;
+      clip_state[6] = 0.0f;
+      clip_state[7] = 0.0f;
+    }
+    if (d.skip) return;
+  }
   float* st = seg_state + (size_t)seg * 4;
   const long long a = seg_off[seg], b = seg_off[seg + 1];
   int in_graph = st[0] > 0.0f;
@@ -47,24 +136,32 @@ __global__ __launch_bounds__(256) void adamw_ema_prepare_kernel(const float* __r
       st[1] = 0.0f;
     }
     if (seg == 0) {
-      step[0] += 1.0f;
-      const float t = ema_state[1] + 1.0f;
-      float w = 1.0f - ema_decay;
-      if (ema_warmup >= 1.0f) w = fmaxf(w, (ema_warmup - 1.0f) / (ema_warmup + t));
-      ema_state[0] = w;
-      ema_state[1] = t;
+      step[0] += 1.0f;                         // completed optimizer steps (the value torch keeps for every updated parameter)
+      if constexpr (EMA) {
+        const float t = ema_state[1] + 1.0f;
+        float w = 1.0f - ema_decay;
+        if (ema_warmup >= 1.0f) w = fmaxf(w, (ema_warmup - 1.0f) / (ema_warmup + t));
+        ema_state[0] = w;
+        ema_state[1] = t;
+      }
     }
   }
 }
 
-// The average is updated from the p the thread has just formed: 5 loads + 4 stores per element instead of the 4 + 3 of the plain
-// step followed by a 2 + 1 lerp launch.
-__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, float* __restrict__ ema,
-                                                        const long long* __restrict__ seg_off, const float* __restrict__ seg_state,
-                                                        const float* __restrict__ ema_state, int nseg, size_t n, size_t n_nodecay,
-                                                        float lr, float beta1, float beta2, float eps, float wd0, float wd1,
-                                                        float gscale) {
+// EMA: the average is updated from the p the thread has just formed: 5 loads + 4 stores per element instead of the 4 + 3 of the
+// plain step followed by a 2 + 1 lerp launch.  CLIP: the gradient scale is the e the prepare launch left in clip_state[0]; on a
+// skipped step (clip_state[5]) nothing is read or written.
+template <bool EMA, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, float* __restrict__ ema,
+                                                    const long long* __restrict__ seg_off, const float* __restrict__ seg_state,
+                                                    const float* __restrict__ ema_state, const float* __restrict__ clip_state,
+                                                    int nseg, size_t n, size_t n_nodecay, float lr, float beta1, float beta2, float eps,
+                                                    float wd0, float wd1, float gscale) {
+  if constexpr (CLIP) {
+    if (clip_state[5] != 0.0f) return;
+    gscale = clip_state[0];
+  }
   __shared__ long long offS[ADAMW_LDS_SEGS + 1];
   const bool staged = nseg <= ADAMW_LDS_SEGS;
   if (staged) {
@@ -72,7 +169,8 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
     __syncthreads();
   }
   const long long* off = staged ? offS : seg_off;
-  const float w = ema_state[0];
+  float w = 0.0f;
+  if constexpr (EMA) w = ema_state[0];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     int lo = 0, hi = nseg - 1;                 // largest seg with off[seg] <= i
     while (lo < hi) {
@@ -80,7 +178,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
       if ((size_t)off[mid] <= i) lo = mid; else hi = mid - 1;
     }
     const float* st = seg_state + (size_t)lo * 4;
-    if (st[1] == 0.0f) continue;               // parameter not in the graph: p, m, v AND ema are left alone
+    if (st[1] == 0.0f) continue;               // parameter not in the graph: left alone (p, m, v AND ema), as torch skips .grad is None
     const float step_size = st[2], bc2s = st[3];
     const float gi = g[i] * gscale;
     const float wd = (i < n_nodecay) ? wd0 : wd1;
@@ -90,8 +188,10 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
     const float denom = sqrtf(vi) / bc2s + eps;
     pi -= step_size * (mi / denom);
     p[i] = pi; m[i] = mi; v[i] = vi;
-    const float ei = ema[i];
-    ema[i] = ei + w * (pi - ei);
+    if constexpr (EMA) {
+      const float ei = ema[i];
+      ema[i] = ei + w * (pi - ei);
+    }
   }
 }
 
@@ -114,9 +214,55 @@ __global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, fl
   }
 }
 
+// The parameters of one step, shared by the three entries (absent parts null / 0).
+struct AdamWArgs {
+  float *p, *m, *v, *ema, *step, *seg_state, *ema_state, *clip_state;
+  const float* g;
+  const long long* seg_off;
+  double* clip_ws;
+  int nseg, clip_parts;
+  size_t n, n_nodecay;
+  float lr, beta1, beta2, eps, wd0, wd1, gscale, ema_decay, ema_warmup, max_norm;
+};
+
+template <bool EMA, bool CLIP>
+static int launch_adamw(const AdamWArgs& a, hipStream_t s, const char* prepare_name, const char* name) {
+  hipLaunchKernelGGL((adamw_prepare_kernel<EMA, CLIP>), dim3(a.nseg), dim3(256), 0, s, a.g, a.seg_off, a.seg_state, a.step, a.ema_state,
+                     a.clip_state, a.clip_ws, a.clip_parts, a.lr, a.beta1, a.beta2, a.ema_decay, a.ema_warmup, a.gscale, a.max_norm);
+  int rc = check_launch(prepare_name);
+  if (rc) return rc;
+  const int grid = (int)std::min<size_t>((a.n + 255) / 256, 2048);
+  hipLaunchKernelGGL((adamw_kernel<EMA, CLIP>), dim3(grid), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.ema, a.seg_off, a.seg_state, a.ema_state,
+                     a.clip_state, a.nseg, a.n, a.n_nodecay, a.lr, a.beta1, a.beta2, a.eps, a.wd0, a.wd1, a.gscale);
+  return check_launch(name);
+}
+
+static int check_ema_ranges(const char* who, float ema_decay, float ema_warmup) {
+  if (!(ema_decay >= 0.0f && ema_decay < 1.0f)) {               // NaN fails both comparisons
+    set_error("%s: ema_decay = %g is outside [0, 1)", who, (double)ema_decay);
+    return A3D_ERR_ARG;
+  }
+  if (!(ema_warmup == 0.0f || (ema_warmup >= 1.0f && std::isfinite(ema_warmup)))) {
+    set_error("%s: ema_warmup = %g must be 0 (off) or a finite value >= 1", who, (double)ema_warmup);
+    return A3D_ERR_ARG;
+  }
+  return A3D_OK;
+}
+
 }  // namespace a3d
 
 using namespace a3d;
+
+extern "C" int a3d_adamw_step(float* p, const float* g, float* m, float* v, float* step, const long long* seg_off,
+                              float* seg_state, int nseg, size_t n, size_t n_nodecay, float lr, float beta1, float beta2, float eps,
+                              float wd_nodecay, float wd_decay, float grad_scale, void* stream) {
+  if (!p || !g || !m || !v || !step || !seg_off || !seg_state) { set_error("a3d_adamw_step: null pointer"); return A3D_ERR_ARG; }
+  if (n == 0) return A3D_OK;
+  if (nseg <= 0) { set_error("a3d_adamw_step: the flat buffer needs at least one parameter segment (nseg = %d)", nseg); return A3D_ERR_ARG; }
+  const AdamWArgs a = {p, m, v, nullptr, step, seg_state, nullptr, nullptr, g, seg_off, nullptr, nseg, 0, n, n_nodecay,
+                       lr, beta1, beta2, eps, wd_nodecay, wd_decay, grad_scale, 0.0f, 0.0f, 0.0f};
+  return launch_adamw<false, false>(a, (hipStream_t)stream, "a3d_adamw_step(prepare)", "a3d_adamw_step");
+}
 
 extern "C" int a3d_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, float* step, const long long* seg_off,
                                   float* seg_state, float* ema_state, int nseg, size_t n, size_t n_nodecay, float lr, float beta1,
@@ -130,24 +276,48 @@ extern "C" int a3d_adamw_ema_step(float* p, const float* g, float* m, float* v, 
     set_error("a3d_adamw_ema_step: the flat buffer needs at least one parameter segment (nseg = %d)", nseg);
     return A3D_ERR_ARG;
   }
-  if (!(ema_decay >= 0.0f && ema_decay < 1.0f)) {               // NaN fails both comparisons
-    set_error("a3d_adamw_ema_step: ema_decay = %g is outside [0, 1)", (double)ema_decay);
+  if (check_ema_ranges("a3d_adamw_ema_step", ema_decay, ema_warmup)) return A3D_ERR_ARG;
+  if (n == 0) return A3D_OK;
+  const AdamWArgs a = {p, m, v, ema, step, seg_state, ema_state, nullptr, g, seg_off, nullptr, nseg, 0, n, n_nodecay,
+                       lr, beta1, beta2, eps, wd_nodecay, wd_decay, grad_scale, ema_decay, ema_warmup, 0.0f};
+  return launch_adamw<true, false>(a, (hipStream_t)stream, "a3d_adamw_ema_step(prepare)", "a3d_adamw_ema_step");
+}
+
+extern "C" int a3d_adamw_clip_step(float* p, const float* g, float* m, float* v, float* ema, float* step, const long long* seg_off,
+                                   float* seg_state, float* ema_state, float* clip_state, double* clip_ws, int nseg, size_t n,
+                                   size_t n_nodecay, float lr, float beta1, float beta2, float eps, float wd_nodecay, float wd_decay,
+                                   float grad_scale, float ema_decay, float ema_warmup, float max_norm, void* stream) {
+  if (!p || !g || !m || !v || !step || !seg_off || !seg_state || !clip_state || !clip_ws) {
+    set_error("a3d_adamw_clip_step: null pointer");
     return A3D_ERR_ARG;
   }
-  if (!(ema_warmup == 0.0f || (ema_warmup >= 1.0f && std::isfinite(ema_warmup)))) {
-    set_error("a3d_adamw_ema_step: ema_warmup = %g must be 0 (off) or a finite value >= 1", (double)ema_warmup);
+  if ((ema == nullptr) != (ema_state == nullptr)) {
+    set_error("a3d_adamw_clip_step: ema and ema_state must both be given or both be null");
     return A3D_ERR_ARG;
   }
+  if (nseg <= 0) {
+    set_error("a3d_adamw_clip_step: the flat buffer needs at least one parameter segment (nseg = %d)", nseg);
+    return A3D_ERR_ARG;
+  }
+  if (!(max_norm > 0.0f)) {                                     // NaN fails the comparison; +inf is legal (measure only)
+    set_error("a3d_adamw_clip_step: max_norm = %g must be > 0 (+inf: measure the norm, never clip)", (double)max_norm);
+    return A3D_ERR_ARG;
+  }
+  if (ema && check_ema_ranges("a3d_adamw_clip_step", ema_decay, ema_warmup)) return A3D_ERR_ARG;
   if (n == 0) return A3D_OK;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(adamw_ema_prepare_kernel, dim3(nseg), dim3(256), 0, s, g, seg_off, seg_state, step, ema_state, lr, beta1, beta2,
-                     ema_decay, ema_warmup);
-  int rc = check_launch("a3d_adamw_ema_step(prepare)");
+  const size_t head = std::min<size_t>(((16u - ((uintptr_t)g & 15u)) & 15u) / 4u, n);
+  const size_t nvec = (n - head) / 4;
+  // always CLIP_PARTS workgroups would leave most of them idle on a small buffer; the idle ones' partials are simply not written and
+  // not read: the prepare launch is told how many there are
+  const int parts = (int)std::min<size_t>(std::max<size_t>((nvec + 255) / 256, 1), CLIP_PARTS);
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(parts), dim3(256), 0, s, g, n, head, nvec, clip_ws);
+  int rc = check_launch("a3d_adamw_clip_step(norm)");
   if (rc) return rc;
-  const int grid = (int)std::min<size_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(adamw_ema_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, ema, seg_off, seg_state, ema_state, nseg, n, n_nodecay,
-                     lr, beta1, beta2, eps, wd_nodecay, wd_decay, grad_scale);
-  return check_launch("a3d_adamw_ema_step");
+  const AdamWArgs a = {p, m, v, ema, step, seg_state, ema_state, clip_state, g, seg_off, clip_ws, nseg, parts, n, n_nodecay,
+                       lr, beta1, beta2, eps, wd_nodecay, wd_decay, grad_scale, ema_decay, ema_warmup, max_norm};
+  return ema ? launch_adamw<true, true>(a, s, "a3d_adamw_clip_step(prepare)", "a3d_adamw_clip_step")
+             : launch_adamw<false, true>(a, s, "a3d_adamw_clip_step(prepare)", "a3d_adamw_clip_step");
 }
 
 extern "C" int a3d_swap_f32(float* a, float* b, size_t n, void* stream) {

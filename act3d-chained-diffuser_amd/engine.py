@@ -9,6 +9,7 @@ TrainTester.train_one_step (main_keypose.py:207-234, main_trajectory.py:177-204)
 The reference's CLI, data loaders, tensorboard and evaluation loop are out of scope.
 """
 import contextlib
+import ctypes
 import math
 import os
 
@@ -104,17 +105,39 @@ def _check_ema(ema_decay, ema_warmup):
     return d, w
 
 
+def _check_max_grad_norm(max_grad_norm):
+    """The range a3d_adamw_clip_step accepts for max_norm, checked where the keyword enters.  Returns None (off) or a float;
+    +inf is legal: the norm is measured and non-finite steps are skipped, but nothing is ever clipped."""
+    if max_grad_norm is None:
+        return None
+    x = float(max_grad_norm)
+    if not (x > 0.0 and ctypes.c_float(x).value > 0.0):      # NaN fails the comparison; the kernel takes an fp32
+        raise ValueError("max_grad_norm = %r must be > 0 (None: no clipping)" % (max_grad_norm,))
+    return x
+
+
 class FlatAdamW:
     """torch.optim.AdamW semantics (lr, betas, eps, two weight-decay groups) as one fused kernel over FlatParams.
 
     With `ema_decay` the same launch also keeps an exponential moving average of the weights (`ema`, a second flat buffer;
     DESIGN 4.21): decay min(ema_decay, (1 + t) / (ema_warmup + t)) at the t-th EMA update, t counted on the device
     (`ema_updates`).  The averages are read by exchanging them with the weights IN PLACE (`swap_ema`, `ema_weights()`): the
-    parameters are views of flat.flat and every captured graph addresses that buffer, so nothing is rebound."""
+    parameters are views of flat.flat and every captured graph addresses that buffer, so nothing is rebound.
 
-    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4, ema_decay=None, ema_warmup=10):
+    With `max_grad_norm` the step clips the global norm of the (grad_scale-averaged) gradient to that value and skips a step whose
+    norm is not finite, both decided on the device inside the same call: `grad_norm`, `clip_scale`, `clipped_steps`,
+    `skipped_steps`, `last_step_skipped` are views of the device state.  That state is not part of state_dict() / checkpoints."""
+
+    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4, ema_decay=None, ema_warmup=10,
+                 max_grad_norm=None):
         self.flat, self.betas, self.eps, self.weight_decay = flat, betas, eps, weight_decay
         self.ema_decay, self.ema_warmup = _check_ema(ema_decay, ema_warmup)
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.clip_state = self.clip_ws = None
+        if self.max_grad_norm is not None:
+            # {e applied, norm, coef, clipped steps, skipped steps, last step skipped, 0, 0} and the norm pass's partials
+            self.clip_state = torch.zeros(8, device=flat.flat.device, dtype=torch.float32)
+            self.clip_ws = torch.zeros(L.ADAMW_CLIP_WS_DOUBLES, device=flat.flat.device, dtype=torch.float64)
         self.ema = self.ema_state = None
         self.ema_swapped = False                 # True while flat.flat holds the averages and `ema` the raw weights
         if self.ema_decay is not None:
@@ -146,10 +169,19 @@ class FlatAdamW:
 
     def step(self, grad_scale=1.0):
         f = self.flat
+        if self.ema is not None and self.ema_swapped:
+            raise RuntimeError("FlatAdamW.step() while the EMA weights are swapped in: it would train the averages "
+                               "(leave ema_weights() / call swap_ema() first)")
+        if self.clip_state is not None:
+            has_ema = self.ema is not None
+            L.call("a3d_adamw_clip_step", f.flat.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
+                   self.exp_avg_sq.data_ptr(), self.ema.data_ptr() if has_ema else None, self.step_count.data_ptr(),
+                   self.seg_off.data_ptr(), self.seg_state.data_ptr(), self.ema_state.data_ptr() if has_ema else None,
+                   self.clip_state.data_ptr(), self.clip_ws.data_ptr(), len(f.order), f.n, f.n_nodecay, float(self.lr),
+                   self.betas[0], self.betas[1], self.eps, 0.0, float(self.weight_decay), float(grad_scale),
+                   self.ema_decay if has_ema else 0.0, self.ema_warmup if has_ema else 0.0, self.max_grad_norm, L.stream())
+            return
         if self.ema is not None:
-            if self.ema_swapped:
-                raise RuntimeError("FlatAdamW.step() while the EMA weights are swapped in: it would train the averages "
-                                   "(leave ema_weights() / call swap_ema() first)")
             L.call("a3d_adamw_ema_step", f.flat.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
                    self.exp_avg_sq.data_ptr(), self.ema.data_ptr(), self.step_count.data_ptr(), self.seg_off.data_ptr(),
                    self.seg_state.data_ptr(), self.ema_state.data_ptr(), len(f.order), f.n, f.n_nodecay, float(self.lr),
@@ -171,6 +203,40 @@ class FlatAdamW:
         self.exp_avg.zero_(); self.exp_avg_sq.zero_(); self.step_count.zero_(); self.seg_state.zero_()
         if self.ema is not None:
             self.reset_ema()
+        if self.clip_state is not None:
+            self.clip_state.zero_()
+
+    # ---- gradient-norm clipping (max_grad_norm is not None): views of the device state, none of them synchronises
+    def _clip_slot(self, what, k):
+        if self.clip_state is None:
+            raise RuntimeError("%s: this optimizer does not clip (built with max_grad_norm=None)" % what)
+        return self.clip_state[k]
+
+    @property
+    def grad_norm(self):
+        """Global L2 norm of the last step's gradient, grad_scale included, before clipping (clip_state[1])."""
+        return self._clip_slot("grad_norm", 1)
+
+    @property
+    def clip_scale(self):
+        """The factor the last step multiplied every gradient element by: grad_scale * min(1, max_grad_norm / (norm + 1e-6)),
+        0 on a skipped step (clip_state[0]) -- what a3d_adamw_step / a3d_adamw_ema_step would take as grad_scale."""
+        return self._clip_slot("clip_scale", 0)
+
+    @property
+    def clipped_steps(self):
+        """Steps whose norm exceeded max_grad_norm so far (clip_state[3])."""
+        return self._clip_slot("clipped_steps", 3)
+
+    @property
+    def skipped_steps(self):
+        """Steps skipped for a non-finite gradient norm so far (clip_state[4])."""
+        return self._clip_slot("skipped_steps", 4)
+
+    @property
+    def last_step_skipped(self):
+        """1.0 if the last step was skipped, else 0.0 (clip_state[5])."""
+        return self._clip_slot("last_step_skipped", 5)
 
     # ---- EMA of the weights (ema_decay is not None)
     def _need_ema(self, what):
@@ -277,14 +343,16 @@ class FlatAdamW:
         self.lr = sd["param_groups"][0].get("lr", self.lr)
 
 
-def get_optimizer(model, lr=1e-4, active_names=None, ema_decay=None, ema_warmup=10):
+def get_optimizer(model, lr=1e-4, active_names=None, ema_decay=None, ema_warmup=10, max_grad_norm=None):
     """engine.py:89-102 on the flat buffers.  Returns (FlatParams, FlatAdamW).  With active_names=None every trainable
     parameter is placed in the buffer; parameters that never receive a gradient are left untouched by the fused AdamW kernel
     (as torch.optim.AdamW skips parameters whose .grad is None -- no weight decay on unused FPN blocks).  ema_decay / ema_warmup:
-    FlatAdamW's EMA of the weights (off by default)."""
+    FlatAdamW's EMA of the weights (off by default).  max_grad_norm: FlatAdamW's global gradient-norm clipping + non-finite step
+    skip (off by default)."""
     _check_ema(ema_decay, ema_warmup)                # before the parameters are re-homed
+    _check_max_grad_norm(max_grad_norm)
     flat = FlatParams(model, active_names)
-    return flat, FlatAdamW(flat, lr=lr, ema_decay=ema_decay, ema_warmup=ema_warmup)
+    return flat, FlatAdamW(flat, lr=lr, ema_decay=ema_decay, ema_warmup=ema_warmup, max_grad_norm=max_grad_norm)
 
 
 DP_ONESHOT = os.environ.get("A3D_DP_ONESHOT", "0") == "1"

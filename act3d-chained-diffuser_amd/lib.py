@@ -161,6 +161,7 @@ SIGNATURES = {
     "a3d_adamw_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _z, _z, _f, _f, _f, _f, _f, _f, _f, _p]),
     # optim.hip
     "a3d_adamw_ema_step": (_i, [_p] * 9 + [_i, _z, _z] + [_f] * 9 + [_p]),
+    "a3d_adamw_clip_step": (_i, [_p] * 11 + [_i, _z, _z] + [_f] * 10 + [_p]),
     "a3d_swap_f32": (_i, [_p, _p, _z, _p]),
     "a3d_dbg_mfma_bf16": (_i, [_p, _p, _p, _p]),
     "a3d_dbg_mfma_f32": (_i, [_p, _p, _p, _p]),
@@ -205,6 +206,9 @@ SIGNATURES = {
     "a3d_resize_crop": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _p]),
     "a3d_traj_update": (_i, [_p, _p, _p, _i, _i, _i, _p]),
 }
+
+# doubles in a3d_adamw_clip_step's clip_ws = workgroups of its norm pass (A3D_ADAMW_CLIP_WS_DOUBLES in the header)
+ADAMW_CLIP_WS_DOUBLES = 256
 
 _lib = None
 

@@ -278,7 +278,8 @@ class BaseTrainTester:
     def get_optimizer(self, model):
         """The reference's two AdamW groups (engine.py:89-102) as ONE fused optimizer over flat buffers (`optimizer.flat`)."""
         return E.get_optimizer(model, lr=self.args.lr, ema_decay=getattr(self.args, "ema_decay", None) or None,
-                               ema_warmup=getattr(self.args, "ema_warmup", 10))[1]
+                               ema_warmup=getattr(self.args, "ema_warmup", 10),
+                               max_grad_norm=getattr(self.args, "max_grad_norm", None) or None)[1]
 
     def _eval_weights(self, optimizer):
         """The weights an evaluation reads: the optimizer's EMA (swapped in for the duration) with args.ema_eval (default 1)
@@ -337,10 +338,14 @@ class BaseTrainTester:
                                           accumulate=getattr(self.args, "accumulate_grad_batches", 1))
         return r
 
-    def _log_train(self, loss, step_id):
+    def _log_train(self, loss, step_id, optimizer=None):
         if self.writer is not None and (step_id + 1) % self.args.val_freq == 0:
             self.writer.add_scalar("lr", self.args.lr, step_id)
             self.writer.add_scalar("train-loss/noise_mse", loss, step_id)
+            if getattr(optimizer, "clip_state", None) is not None:        # the optimizer clips: its device counters, read only here
+                self.writer.add_scalar("train-stats/grad_norm", optimizer.grad_norm, step_id)
+                self.writer.add_scalar("train-stats/clip_scale", optimizer.clip_scale, step_id)
+                self.writer.add_scalar("train-stats/skipped_steps", optimizer.skipped_steps, step_id)
 
     def load_checkpoint(self, model, optimizer):
         """Weights + optimizer state from args.checkpoint; the learning rate is reset to args.lr as the reference does
@@ -446,7 +451,7 @@ class KeyposeTrainTester(BaseTrainTester):
         runner.fwd_bwd = lambda m, c, s, cb: E.fwd_bwd_keypose(m, c, s, use_gt, cb)
         runner.eager_step = eager
         loss = runner(step_id, sample)
-        self._log_train(loss, step_id)
+        self._log_train(loss, step_id, optimizer)
         return loss
 
     @torch.no_grad()
@@ -500,7 +505,7 @@ class TrajectoryTrainTester(BaseTrainTester):
         runner = self._runner_for(model, criterion, optimizer, eager)
         runner.eager_step = eager
         loss = runner(step_id, sample)
-        self._log_train(loss, step_id)
+        self._log_train(loss, step_id, optimizer)
         return loss
 
     @torch.no_grad()

@@ -380,6 +380,27 @@ int a3d_adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema,
                        float* seg_state, float* ema_state, int nseg, size_t n, size_t n_nodecay, float lr, float beta1, float beta2,
                        float eps, float wd_nodecay, float wd_decay, float grad_scale, float ema_decay, float ema_warmup,
                        void* stream);
+/* a3d_adamw_step / a3d_adamw_ema_step behind global gradient-norm clipping and a non-finite-step skip, both decided on the device
+ * (csrc/optim.hip; the reference has neither).  ema and ema_state may both be null (no average is kept) or both be given.  Three
+ * launches on the stream, no host sync, no allocation:
+ *   norm    : sum g[i]^2 over all n elements in double, one partial per workgroup in clip_ws (A3D_ADAMW_CLIP_WS_DOUBLES doubles, caller
+ *             owned, no initialisation needed); no floating-point atomics, partials combined in a fixed order: the same input gives
+ *             the same bits.
+ *   prepare : norm = fp32(|grad_scale| sqrt(sum)), coef = min(1, max_norm / (norm + 1e-6)) in fp32 (torch's clip_grad_norm_;
+ *             max_norm = +inf gives coef == 1 exactly: measure only), e = fp32(grad_scale coef); then a3d_adamw_step's prepare.
+ *   update  : the update of a3d_adamw_step / a3d_adamw_ema_step with gi = g[i] e: p, m, v, step, seg_state, ema and ema_state end
+ *             bit for bit what those entries leave when called with grad_scale = e.
+ * A non-finite norm (a NaN or inf gradient element, or a norm beyond fp32) ALWAYS skips the step: p, m, v, step, seg_state, ema and
+ * ema_state stay untouched, and a parameter whose first non-zero gradient arrives in that step does not join.
+ * clip_state [8] (zero-initialised by the caller) = {e applied (0 on a skipped step), norm, coef (0 on a skipped step), number of
+ * steps with coef < 1, number of skipped steps, 1 if the last step was skipped else 0, 0, 0}; the counters are floats, exact to 2^24.
+ * -22 for a null pointer (other than ema AND ema_state), exactly one of ema / ema_state null, nseg <= 0, max_norm NaN or <= 0, and
+ * a3d_adamw_ema_step's ema_decay / ema_warmup ranges when an average is given.  n == 0 returns 0. */
+#define A3D_ADAMW_CLIP_WS_DOUBLES 256
+int a3d_adamw_clip_step(float* p, const float* g, float* m, float* v, float* ema, float* step, const long long* seg_off,
+                        float* seg_state, float* ema_state, float* clip_state, double* clip_ws, int nseg, size_t n, size_t n_nodecay,
+                        float lr, float beta1, float beta2, float eps, float wd_nodecay, float wd_decay, float grad_scale,
+                        float ema_decay, float ema_warmup, float max_norm, void* stream);
 /* a[i] <-> b[i] for i < n in one pass (csrc/optim.hip); replaces torch's three-copy exchange through a temporary (tmp = a.clone();
  * a.copy_(b); b.copy_(tmp)).  Any n, pointers only 4-byte aligned.  -22 for a null pointer with n > 0 or overlapping ranges. */
 int a3d_swap_f32(float* a, float* b, size_t n, void* stream);
