@@ -18,8 +18,7 @@ import random
 
 import torch
 
-from .diffusion import RANK_MAX_CANDIDATES, check_scene, check_clearance_args, check_num_samples, check_rot_weight, check_scene_select, \
-    check_guide, check_guide_shape
+from .diffusion import check_sampling_call, _graph_replay
 
 _TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight",
             "scene_mask", "clear_margin", "clear_skip", "guide")
@@ -212,32 +211,19 @@ class Actioner:
         key = (tuple((tuple(t.shape), t.dtype, t.device) for t in ins), ghost_points is not None, share,
                kp.backbone_dtype, kp.fpn_dtype,
                None if not share else (self._traj_model.prediction_head.backbone_dtype, self._traj_model.prediction_head.fpn_dtype))
-        gr = self._graph
-        if gr is None or gr["key"] != key:
+
+        def capture():
+            # "static" and "out" keep every buffer the captured launches address alive
             static = [t.clone() for t in ins]
             run = lambda: self._keypose_half(static[0], static[1], static[2], static[3], static[4:] if ghost_points is not None else None,
                                              share)
-            # warm-up (allocator, lazy module state, the convolution library's algorithm choice) on a side stream outside capture;
-            # it must not consume ghost-point draws: the sampler state is put back, so a replay draws what an eager call would
+            # the warm-up (allocator, lazy module state, the convolution library's algorithm choice) must not consume ghost-point
+            # draws: the sampler state is put back, so a replay draws what an eager call would
             rng = kp._rng_state.clone() if hasattr(kp, "_rng_state") else None
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                run()
-                if rng is not None:
-                    kp._rng_state.copy_(rng)
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            # "static" and "out" keep every buffer the captured launches address alive
-            gr = self._graph = {"key": key, "static": static}
-            with torch.cuda.graph(g):
-                gr["out"] = run()
-            gr["g"] = g
-        # refresh the captured input buffers in place (same addresses; the key pins every shape and dtype)
-        for dst, src in zip(gr["static"], ins):
-            dst.copy_(src)
-        gr["g"].replay()
-        return gr["out"]
+            return run, {"static": static}, None if rng is None else (lambda: kp._rng_state.copy_(rng))
+
+        self._graph = _graph_replay(self._graph, key, capture, ins)
+        return self._graph["out"]
 
     # ------------------------------------------------------------------------------------------------ predict
     @torch.no_grad()
@@ -254,36 +240,16 @@ class Actioner:
         bad = [k for k in sample_kw if k not in _TRAJ_KW]
         if bad:
             raise TypeError("predict() got unexpected keyword arguments %s" % bad)
-        if sample_kw.get("select") is not None:
-            # the ranking's own argument errors, before the keypose half launches anything
-            if not self._predict_trajectory:
+        if not self._predict_trajectory:
+            if sample_kw.get("select") is not None:
                 raise ValueError("select ranks sampled trajectories: it needs predict_trajectory=True")
-            if sample_kw.get("num_samples") is None:
-                raise ValueError("select ranks the candidates of a num_samples=G call: give num_samples")
-            if check_num_samples(sample_kw["num_samples"]) > RANK_MAX_CANDIDATES:
-                raise ValueError("select serves at most %d candidates per scene, num_samples is %d" % (
-                    RANK_MAX_CANDIDATES, sample_kw["num_samples"]))
-            _, w_clear = check_scene_select(sample_kw["select"], True, True, True)
-            check_rot_weight(sample_kw.get("rot_weight", 1.0))
-            if w_clear != 0.0:
-                if not torch.is_tensor(pcds) or pcds.dim() != 6:
-                    raise ValueError("pcds must be (B, history, cameras, 3, H, W)")
-                check_scene(pcds[:, -1], sample_kw.get("scene_mask"), pcds.shape[0])
-                check_clearance_args(sample_kw.get("clear_margin", 0.05), sample_kw.get("clear_skip", (1, 1)))
-        if sample_kw.get("guide") is not None:
-            # the guide step's own argument errors, before the keypose half launches anything
-            if not self._predict_trajectory:
+            if sample_kw.get("guide") is not None:
                 raise ValueError("guide steers sampled trajectories: it needs predict_trajectory=True")
-            check_guide(sample_kw["guide"])
-            if not torch.is_tensor(pcds) or pcds.dim() != 6:
-                raise ValueError("pcds must be (B, history, cameras, 3, H, W)")
-            if not torch.is_tensor(trajectory_mask) or trajectory_mask.dim() != 2:
-                raise ValueError("guide needs trajectory_mask (B, L)")
-            G = sample_kw.get("num_samples")
-            check_guide_shape(1 if G is None else check_num_samples(G), trajectory_mask.shape[1], self._action_dim + 2)
-            check_scene(pcds[:, -1], sample_kw.get("scene_mask"), pcds.shape[0])
-            check_clearance_args(sample_kw.get("clear_margin", 0.05), sample_kw.get("clear_skip", (1, 1)))
         self._check(rgbs, pcds, gripper, gt_action, trajectory_mask, use_graph, ghost_points)
+        if self._predict_trajectory:
+            # the sampling call's own argument errors, before the keypose half launches anything (the schedule and the noise
+            # tables stay compute_trajectory's: it knows the chain length)
+            check_sampling_call(pcds.shape[0], trajectory_mask.shape[1], self._action_dim + 2, None, pcds[:, -1], True, **sample_kw)
         share = self._sharing()
         output = {"action": None, "attention": {}}
         B = rgbs.shape[0]

@@ -688,49 +688,75 @@ class DiffusionHead(nn.Module):
             self._sem_cache[key] = O.sinusoidal_emb(torch.arange(Ln, device=device, dtype=torch.float32), E)
         return self._sem_cache[key]
 
-    def encode_context(self, visual_tokens, ctx_xyz, instruction, curr_gripper, goal_gripper, drop=None):
-        """Step-invariant context (diffusion_head.py:222-247, 290-323): returns (ctx (B,S,E), ctx_xyz (B,S,3), instr)."""
-        B = visual_tokens.shape[0]
-        instr = O.linear(instruction.float(), self.instruction_encoder) if self.use_instruction else None
-        ctx = visual_tokens
-        if self.use_instruction:
-            ctx = self.vl_attention[0](ctx, None, instr, drop=drop)
+    def _gripper_tokens(self, curr_gripper, goal_gripper):
+        """The gripper tokens every context ends with: (rows (B, 1 | 2, E), the list of their xyz rows (B, 1, 3) each) -- the
+        current gripper and, with use_goal, the goal."""
+        B = curr_gripper.shape[0]
         cg = O.linear(curr_gripper, self.curr_gripper_encoder)[:, None] + broadcast_row(self.curr_gripper_embed.weight, B, 1)
         extra, extra_xyz = [cg], [curr_gripper[:, None, :3]]
         if self.use_goal:
             gg = O.linear(goal_gripper, self.goal_gripper_encoder)[:, None] + broadcast_row(self.goal_gripper_embed.weight, B, 1)
             extra.append(gg)
             extra_xyz.append(goal_gripper[:, None, :3])
-        ctx = O.BuildContextFn.apply(ctx, None, torch.cat(extra, dim=1))
+        return torch.cat(extra, dim=1), extra_xyz
+
+    def encode_context(self, visual_tokens, ctx_xyz, instruction, curr_gripper, goal_gripper, drop=None):
+        """Step-invariant context (diffusion_head.py:222-247, 290-323): returns (ctx (B,S,E), ctx_xyz (B,S,3), instr)."""
+        instr = O.linear(instruction.float(), self.instruction_encoder) if self.use_instruction else None
+        ctx = visual_tokens
+        if self.use_instruction:
+            ctx = self.vl_attention[0](ctx, None, instr, drop=drop)
+        extra, extra_xyz = self._gripper_tokens(curr_gripper, goal_gripper)
+        ctx = O.BuildContextFn.apply(ctx, None, extra)
         ctx_xyz = torch.cat([ctx_xyz] + extra_xyz, dim=1).contiguous()
         return ctx, ctx_xyz, instr
+
+    def _iteration(self, l, prev, trajectory_mask, traj_feats, traj_xyz, sem, silu_t, ctx, ctx_xyz, instr, drop=None, sinks=None,
+                   cache=None):
+        """Iteration l of the head (diffusion_head.py:325-363) on module set l: the optional language layer, the trajectory,
+        position and rotation stacks, the two regressors; returns `prev` updated by the prediction (xyz accumulates, the rotation
+        is replaced).  traj_feats / traj_xyz / sem / silu_t: the trajectory encoding, its positions, the step embedding rows and
+        SiLU(time embedding), all the caller's.  What differs between the callers comes in:
+          drop   the DropCtx of this iteration (None: no dropout);
+          sinks  the registry of the context's shared gradient sink (ops.GradSink: the k | v projections' input and weight
+                 gradients of all 8 cross-attention layers run as ONE GEMM each when the last layer's backward has parked its
+                 rows), attached after the language layer; None: no sink -- it would change the summation order of the gradients;
+          cache  build_kv_cache's K/V operands: every cross-attention block reads them, ctx / ctx_xyz / instr are unused."""
+        ms = self._mlp_sites
+        stacks = (self.traj_attention[l], self.pos_attention[l], self.rot_attention[l])
+        lang_c, stack_c = None, (None, None, None)
+        if cache is not None:
+            per_layer = iter(cache["ctx"])                  # in _cross_layers order
+            lang_c, stack_c = [cache.get("lang")], [[next(per_layer) for _ in st.layers] for st in stacks]
+        if self.use_instruction:
+            traj_feats = self.traj_lang_attention[l](traj_feats, trajectory_mask, instr, seq1_sem_pos=sem, drop=drop,
+                                                     cross_caches=lang_c)
+        if sinks is not None:
+            ctx = O.attach_grad_sink(ctx, sinks)
+        kw = dict(seq1_xyz=traj_xyz, seq2_xyz=ctx_xyz, seq1_sem_pos=sem, silu_t=silu_t, drop=drop)
+        traj_feats = stacks[0](traj_feats, trajectory_mask, ctx, cross_caches=stack_c[0], **kw)
+        pos_feats = stacks[1](traj_feats, trajectory_mask, ctx, cross_caches=stack_c[1], **kw)
+        rot_feats = stacks[2](traj_feats, trajectory_mask, ctx, cross_caches=stack_c[2], **kw)
+        upd = torch.cat([O.mlp(pos_feats, self.pos_regressor[l][0], self.pos_regressor[l][3], drop=drop,
+                               site_hidden=ms[f"pos_regressor.{l}"]),
+                         O.mlp(rot_feats, self.rot_regressor[l][0], self.rot_regressor[l][3], drop=drop,
+                               site_hidden=ms[f"rot_regressor.{l}"])], dim=-1)
+        return O.TrajUpdateFn.apply(prev, upd)
 
     def forward_tokens(self, trajectory, trajectory_mask, timestep, ctx, ctx_xyz, instr, drop=None):
         """The step-dependent part of DiffusionHead.forward (diffusion_head.py:214-219, 325-363) with autograd."""
         B, Ln, _ = trajectory.shape
         E = ctx.shape[-1]
         trajectory = trajectory.contiguous()
-        ms = self._mlp_sites
-        traj_feats = O.mlp(trajectory, self.traj_encoder[0], self.traj_encoder[3], drop=drop, site_hidden=ms["traj_encoder"])
+        traj_feats = O.mlp(trajectory, self.traj_encoder[0], self.traj_encoder[3], drop=drop,
+                           site_hidden=self._mlp_sites["traj_encoder"])
         traj_xyz = trajectory[..., :3].contiguous()
         time_feats = O.sinusoidal_emb(timestep.float(), E)
         silu_t = O.SiLUFn.apply(time_feats)
         sem = self._sem(Ln, E, trajectory.device)
-        if self.use_instruction:
-            traj_feats = self.traj_lang_attention[0](traj_feats, trajectory_mask, instr, seq1_sem_pos=sem, drop=drop)
-        kw = dict(seq1_xyz=traj_xyz, seq2_xyz=ctx_xyz, seq1_sem_pos=sem, silu_t=silu_t, drop=drop)
-        # the context feeds the k | v projections of all 8 cross-attention layers: one shared gradient sink (ops.GradSink: the
-        # projections' input and weight gradients run as ONE GEMM each when the last layer's backward has parked its rows)
         self._ctx_sinks = []
-        ctx = O.attach_grad_sink(ctx, self._ctx_sinks)
-        traj_feats = self.traj_attention[0](traj_feats, trajectory_mask, ctx, **kw)
-        pos_feats = self.pos_attention[0](traj_feats, trajectory_mask, ctx, **kw)
-        rot_feats = self.rot_attention[0](traj_feats, trajectory_mask, ctx, **kw)
-        upd = torch.cat([O.mlp(pos_feats, self.pos_regressor[0][0], self.pos_regressor[0][3], drop=drop,
-                               site_hidden=ms["pos_regressor.0"]),
-                         O.mlp(rot_feats, self.rot_regressor[0][0], self.rot_regressor[0][3], drop=drop,
-                               site_hidden=ms["rot_regressor.0"])], dim=-1)
-        return O.TrajUpdateFn.apply(trajectory, upd)
+        return self._iteration(0, trajectory, trajectory_mask, traj_feats, traj_xyz, sem, silu_t, ctx, ctx_xyz, instr, drop=drop,
+                               sinks=self._ctx_sinks)
 
     def forward_multi(self, trajectory, trajectory_mask, timestep, tokens, xyzs, instruction, curr_gripper, goal_gripper,
                       new_drop=None):
@@ -743,20 +769,15 @@ class DiffusionHead(nn.Module):
         B, Ln, _ = trajectory.shape
         E = self.curr_gripper_embed.weight.shape[1]
         trajectory = trajectory.contiguous()
-        ms = self._mlp_sites
         drop = new_drop() if new_drop is not None else None
-        traj_feats0 = O.mlp(trajectory, self.traj_encoder[0], self.traj_encoder[3], drop=drop, site_hidden=ms["traj_encoder"])
+        traj_feats0 = O.mlp(trajectory, self.traj_encoder[0], self.traj_encoder[3], drop=drop,
+                            site_hidden=self._mlp_sites["traj_encoder"])
         traj_xyz = trajectory[..., :3].contiguous()
         silu_t = O.SiLUFn.apply(O.sinusoidal_emb(timestep.float(), E))
         sem = self._sem(Ln, E, trajectory.device)
         instr = O.linear(instruction.float(), self.instruction_encoder) if self.use_instruction else None
-        cg = O.linear(curr_gripper, self.curr_gripper_encoder)[:, None] + broadcast_row(self.curr_gripper_embed.weight, B, 1)
-        extra, extra_xyz = [cg], [curr_gripper[:, None, :3]]
-        if self.use_goal:
-            gg = O.linear(goal_gripper, self.goal_gripper_encoder)[:, None] + broadcast_row(self.goal_gripper_embed.weight, B, 1)
-            extra.append(gg)
-            extra_xyz.append(goal_gripper[:, None, :3])
-        extra, extra_xyz = torch.cat(extra, dim=1), torch.cat(extra_xyz, dim=1).contiguous()
+        extra, extra_xyz = self._gripper_tokens(curr_gripper, goal_gripper)
+        extra_xyz = torch.cat(extra_xyz, dim=1).contiguous()
         none = torch.empty((B, 0, E), device=trajectory.device, dtype=torch.float32)
         outs, prev = [], trajectory
         for rnd in range(self.attn_rounds):
@@ -775,18 +796,7 @@ class DiffusionHead(nn.Module):
                 else:
                     ctx = O.BuildContextFn.apply(feats, idx, extra)
                 ctx_xyz = O.gather_rows(xyz, idx, extra_xyz)
-                tf = traj_feats0
-                if self.use_instruction:
-                    tf = self.traj_lang_attention[l](tf, trajectory_mask, instr, seq1_sem_pos=sem, drop=drop)
-                kw = dict(seq1_xyz=traj_xyz, seq2_xyz=ctx_xyz, seq1_sem_pos=sem, silu_t=silu_t, drop=drop)
-                tf = self.traj_attention[l](tf, trajectory_mask, ctx, **kw)
-                pf = self.pos_attention[l](tf, trajectory_mask, ctx, **kw)
-                rf = self.rot_attention[l](tf, trajectory_mask, ctx, **kw)
-                upd = torch.cat([O.mlp(pf, self.pos_regressor[l][0], self.pos_regressor[l][3], drop=drop,
-                                       site_hidden=ms[f"pos_regressor.{l}"]),
-                                 O.mlp(rf, self.rot_regressor[l][0], self.rot_regressor[l][3], drop=drop,
-                                       site_hidden=ms[f"rot_regressor.{l}"])], dim=-1)
-                prev = O.TrajUpdateFn.apply(prev, upd)
+                prev = self._iteration(l, prev, trajectory_mask, traj_feats0, traj_xyz, sem, silu_t, ctx, ctx_xyz, instr, drop=drop)
                 outs.append(prev)
         return outs
 
@@ -806,41 +816,15 @@ class DiffusionHead(nn.Module):
 
     @torch.no_grad()
     def denoise_tokens_cached(self, trajectory, trajectory_mask, t, cache, time_tables):
-        """One network evaluation at integer step t against the prebuilt K/V cache (no autograd, no host sync)."""
+        """One network evaluation at integer step t against the prebuilt K/V cache (no autograd, no host sync): iteration 0 of the
+        head with SiLU(time embedding) read from the time table."""
         B, Ln, _ = trajectory.shape
-        H = self.num_attn_heads
         E = self.curr_gripper_embed.weight.shape[1]
         traj_feats = O.mlp(trajectory, self.traj_encoder[0], self.traj_encoder[3])
         traj_xyz = trajectory[..., :3].contiguous()
         silu_t = time_tables["silu"][t:t + 1].expand(B, E).contiguous()
         sem = self._sem(Ln, E, trajectory.device)
-        if self.use_instruction:
-            lay = self.traj_lang_attention[0].layers[0]
-            q1 = O.AddRowsFn.apply(traj_feats, sem)
-            traj_feats = O.attn_block_cached(q1, traj_feats, None, cache["lang"], lay.cross_12, lay.norm_12, H)
-        li = 0
-
-        def run_stack(x, stack):
-            nonlocal li
-            for lay in stack.layers:
-                q1 = O.AddRowsFn.apply(x, sem)
-                x = O.attn_block_cached(lay.adaln_12(q1, silu_t), x, traj_xyz, cache["ctx"][li], lay.cross_12, lay.norm_12, H)
-                li += 1
-                q1 = O.AddRowsFn.apply(x, sem)
-                qk, vv = lay.adaln_1(q1, silu_t), lay.adaln_1(x, silu_t)
-                x = O.attn_block(qk, qk, vv, x, traj_xyz, traj_xyz, trajectory_mask, lay.sa1, lay.norm_1, H)
-                y = lay.adaln_ff1(x, silu_t)
-                x = O.mlp(y, lay.ffn_12[0], lay.ffn_12[3], lay.norm_122)
-            return x
-
-        traj_feats = run_stack(traj_feats, self.traj_attention[0])
-        keep = li
-        pos_feats = run_stack(traj_feats, self.pos_attention[0])
-        rot_feats = run_stack(traj_feats, self.rot_attention[0])
-        upd = torch.cat([O.mlp(pos_feats, self.pos_regressor[0][0], self.pos_regressor[0][3]),
-                         O.mlp(rot_feats, self.rot_regressor[0][0], self.rot_regressor[0][3])], dim=-1)
-        return O.TrajUpdateFn.apply(trajectory, upd)
-
+        return self._iteration(0, trajectory, trajectory_mask, traj_feats, traj_xyz, sem, silu_t, None, None, None, cache=cache)
 
     # ---- inference, fused: 18 launches per network evaluation (csrc/denoise.hip)
     @torch.no_grad()
@@ -1148,6 +1132,87 @@ def sampler_plan(B, G, Ln, D, E, H, T, cus, multi=False, fused=None, num_inferen
     return SamplerPlan(path, group, scheduled, K, flip_noise, tuple(steps), label)
 
 
+# what check_sampling_call derives from the keywords of a sampling call: G candidates per scene (None: no candidate axis); K steps of
+# the sampler schedule (None: the full chain); the normalised guide (push, smooth, start) or None; the ranking rule's clearance
+# weight (0.0 without one); margin, skip = (head, tail) of the clearance term and cams, pix of the cloud -- None where neither the
+# guide nor the ranking reads the cloud
+_SamplingCall = collections.namedtuple("_SamplingCall", ("G", "K", "guide", "w_clear", "margin", "skip", "cams", "pix"))
+
+
+def check_sampling_call(B, Ln, D, T, pcd_obs, have_goal=True, *, num_samples=None, num_inference_steps=None, scheduler="ddpm", eta=0.0,
+                        init_noise=None, step_noise=None, n_steps=None, select=None, rot_weight=1.0, scene_mask=None,
+                        clear_margin=0.05, clear_skip=(1, 1), guide=None):
+    """Every host-side check of a sampling call (compute_trajectory, Actioner.predict), on shapes and Python values alone: nothing
+    is launched, so a bad argument raises before any kernel runs.  B scenes of Ln steps and D = pose width + 2 signal channels; T:
+    the chain length, or None where the caller leaves the schedule and the noise tables to the sampler (Actioner.predict, whose
+    keypose half these never held up); pcd_obs: the cloud the ranking / the guide would read; the keywords are compute_trajectory's
+    (_TRAJ_KW; n_steps only truncates the step list: nothing to check).  Returns a _SamplingCall."""
+    G = None if num_samples is None else check_num_samples(num_samples)
+    w_clear, scene = 0.0, (None,) * 5
+    if select is not None:
+        if G is None:
+            raise ValueError("select ranks the candidates of a num_samples=G call: give num_samples")
+        if G > RANK_MAX_CANDIDATES:
+            raise ValueError("select serves at most %d candidates per scene, num_samples is %d" % (RANK_MAX_CANDIDATES, G))
+        if D - 2 not in (7, 8):
+            raise ValueError("select ranks pose rows of 7 or 8 channels, curr_gripper has %d" % (D - 2))
+        _, w_clear = check_scene_select(select, have_goal, True, True)
+        check_rot_weight(rot_weight)
+        if w_clear != 0.0:
+            scene = check_scene(pcd_obs, scene_mask, B) + check_clearance_args(clear_margin, clear_skip)
+    K = None
+    if T is not None and (num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0):
+        K = check_sampler_args(T, num_inference_steps, scheduler, eta)
+        if step_noise is not None and step_noise.shape[0] != K:
+            raise ValueError("step_noise has %d leading rows for a schedule of %d steps (one row per step position)"
+                             % (step_noise.shape[0], K))
+    guide = check_guide(guide)
+    if guide is not None:
+        check_guide_shape(G or 1, Ln, D)
+        scene = check_scene(pcd_obs, scene_mask, B) + check_clearance_args(clear_margin, clear_skip)
+    if G is not None and T is not None:
+        check_candidate_noise(init_noise, step_noise, B, G, Ln, D, K or T)
+    cams, pix, margin, sh, st = scene
+    return _SamplingCall(G, K, guide, w_clear, margin, None if sh is None else (sh, st), cams, pix)
+
+
+def _graph_replay(gr, key, capture, srcs, dsts=lambda gr: gr["static"]):
+    """One captured graph per owner (DiffusionPlanner._graph, Actioner._graph): replays the owner's record `gr` (None before the
+    first capture) after refreshing its static inputs from `srcs`, capturing first where gr was taken under another key (shapes,
+    steps, path, schedule, ...).  Returns the record, which the owner keeps: {"key", <what capture() retains>, "out", "g"}.
+    capture() -- called only by a call that captures -- returns (run, keep, after_warmup): run() issues the launches and returns
+    their result; keep is the dict of EVERY buffer the captured launches address (they must stay alive as long as the graph:
+    workspaces, the persistent sampler's tables, the static inputs as keep["static"]); after_warmup (or None) runs on the warm-up
+    stream once the warm-up has been issued, to undo what it must not leave behind.  dsts(gr): the captured tensors srcs go to."""
+    if gr is None or gr["key"] != key:
+        run, keep, after_warmup = capture()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            run()                                           # warm-up (allocator, lazy module state) outside capture
+            if after_warmup is not None:
+                after_warmup()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        gr = dict(key=key, **keep)
+        with torch.cuda.graph(g):
+            gr["out"] = run()
+        gr["g"] = g
+    # refresh the captured buffers in place (same addresses; the key pins every shape and dtype)
+    for dst, src in zip(dsts(gr), srcs):
+        if dst is not src:
+            dst.copy_(src)
+    gr["g"].replay()
+    return gr
+
+
+# the conditioning of a sampling call, the only record that knows both batches: B_scene scenes and B = B_scene x candidates
+# trajectories.  tokens / ctx_xyz (one entry per scale), instruction, cg, gg and trajectory_mask are per scene on the candidate-group
+# path and per trajectory (expanded) on every other; cond_data, cond_mask_u8, kmask, step_noise and traj are per trajectory
+_Conditioned = collections.namedtuple("_Conditioned", ("B_scene", "B", "tokens", "ctx_xyz", "instruction", "cg", "gg", "trajectory_mask",
+                                                       "cond_data", "cond_mask_u8", "kmask", "step_noise", "traj"))
+
+
 class DiffusionPlanner(nn.Module):
 
     def __init__(self, backbone="clip", image_size=(256, 256), embedding_dim=60, output_dim=7,
@@ -1299,95 +1364,83 @@ class DiffusionPlanner(nn.Module):
         (B, L)).  None (default): today's launches and today's bits."""
         head = self.prediction_head
         dev = pcd_obs.device
-        B, Ln = trajectory_mask.shape
-        G = None if num_samples is None else check_num_samples(num_samples)
-        # host-side checks first: bad schedule arguments raise before anything is launched
-        if select is not None:
-            if G is None:
-                raise ValueError("select ranks the candidates of a num_samples=G call: give num_samples")
-            if G > RANK_MAX_CANDIDATES:
-                raise ValueError("select serves at most %d candidates per scene, num_samples is %d" % (RANK_MAX_CANDIDATES, G))
-            if curr_gripper.shape[-1] not in (7, 8):
-                raise ValueError("select ranks pose rows of 7 or 8 channels, curr_gripper has %d" % curr_gripper.shape[-1])
-            _, w_clear = check_scene_select(select, goal_gripper is not None, True, True)
-            check_rot_weight(rot_weight)
-            if w_clear != 0.0:
-                check_scene(pcd_obs, scene_mask, B)
-                check_clearance_args(clear_margin, clear_skip)
-            rank_mask, rank_goal = trajectory_mask, goal_gripper        # per scene: the fallback paths below expand their own copies
-            rank_scene = pcd_obs                                         # the caller's tensor, in world coordinates
-        scheduled = num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0
-        if scheduled:
-            K = check_sampler_args(self.n_steps, num_inference_steps, scheduler, eta)
-            if step_noise is not None and step_noise.shape[0] != K:
-                raise ValueError("step_noise has %d leading rows for a schedule of %d steps (one row per step position)"
-                                 % (step_noise.shape[0], K))
+        B_scene, Ln = trajectory_mask.shape
         D = curr_gripper.shape[-1] + 2
-        guide = check_guide(guide)
-        if guide is not None:
-            check_guide_shape(G or 1, Ln, D)
-            g_cam, g_pix = check_scene(pcd_obs, scene_mask, B)
-            g_margin, g_sh, g_st = check_clearance_args(clear_margin, clear_skip)
-            g_mask = trajectory_mask                                    # per scene: the fallback paths below expand their own copy
-        if G is not None:
-            check_candidate_noise(init_noise, step_noise, B, G, Ln, D, K if scheduled else self.n_steps)
-
+        # host-side checks first: bad arguments raise before anything is launched
+        call = check_sampling_call(B_scene, Ln, D, self.n_steps, pcd_obs, goal_gripper is not None, num_samples=num_samples,
+                                   num_inference_steps=num_inference_steps, scheduler=scheduler, eta=eta, init_noise=init_noise,
+                                   step_noise=step_noise, n_steps=n_steps, select=select, rot_weight=rot_weight, scene_mask=scene_mask,
+                                   clear_margin=clear_margin, clear_skip=clear_skip, guide=guide)
         # ---- the plan: which launches serve the call, from the shapes and the CU count alone
         multi = head.attn_rounds * head.feat_scales > 1
-        plan = sampler_plan(B, G, Ln, D, head.curr_gripper_embed.weight.shape[1], head.num_attn_heads, self.n_steps,
+        plan = sampler_plan(B_scene, call.G, Ln, D, head.curr_gripper_embed.weight.shape[1], head.num_attn_heads, self.n_steps,
                             torch.cuda.get_device_properties(dev).multi_processor_count, multi, fused, num_inference_steps, scheduler,
                             eta, n_steps)
-        group = plan.group
         tb = self.tables(dev)
         sched = self.schedule(dev, plan.K, scheduler, eta) if plan.scheduled else None
-        # tables of the DDPM-step kernels and of the AdaLN modulation: by timestep (full chain) or by step position (schedule)
-        tables, time_sin = (tb, self._time_tables["sin"]) if sched is None else (sched, sched.time_sin)
+        c = self._condition(plan, sched, call.G, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper,
+                            init_noise, step_noise, visual_tokens, fused_conditioning)
+        replay = use_graph and not return_trace
+        state, static, key, gd = self._sampler_state(plan, sched, call, c, pcd_obs, trajectory_mask, scene_mask, fused_conditioning,
+                                                     replay)
+        if call.G is not None:
+            self._last_state = state                        # tests read the leading dimensions of the cache
+        self.last_sampler_path = plan.label                 # which sampler serves this call (read by the bench line and the tests)
+        segments = guided_segments(len(plan.steps), None if call.guide is None else call.guide[2])
+        trace = [] if return_trace else None
+        run = lambda x: self._run_steps(x, plan, tb if sched is None else sched, call, c, state, gd, segments, trace)
+        traj = self._replay(key, run, c.traj, static, state) if replay else run(c.traj)
+        return self._finish(call, c, traj, trace, gd, segments, replay, trajectory_mask, pcd_obs, goal_gripper, select, rot_weight,
+                            scene_mask, clear_margin, clear_skip)
 
-        # ---- conditioning and candidate expansion
+    def _condition(self, plan, sched, G, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, init_noise,
+                   step_noise, visual_tokens, fused_conditioning):
+        """The conditioning of a sampling call -> _Conditioned: visual tokens, the two poses as signals, the in-painting data / mask,
+        the key mask, the candidate reshaping / expansion, the noise defaults and the noisy start trajectory."""
+        dev = pcd_obs.device
+        B_scene, Ln = trajectory_mask.shape
+        D = curr_gripper.shape[-1] + 2
+        B = B_scene * (G or 1)
         tokens, ctx_xyz, cg, gg = self._prepare(rgb_obs, pcd_obs, curr_gripper, goal_gripper, visual_tokens,
                                                 signals=not fused_conditioning)
         tokens, ctx_xyz = _as_list(tokens), _as_list(ctx_xyz)      # one entry per scale
         if fused_conditioning:
             # every per-trajectory conditioning tensor at once, before the candidate expansion below (the kernel expands itself)
-            Gk = 1 if G is None else G
             if init_noise is None:
-                init_noise = torch.randn((B * Gk, Ln, D), device=dev)
+                init_noise = torch.randn((B, Ln, D), device=dev)
             else:
-                init_noise = init_noise.to(dev).float().reshape(B * Gk, Ln, -1)
+                init_noise = init_noise.to(dev).float().reshape(B, Ln, -1)
             cg, gg, cond_data, cond_mask_u8, kmask, traj = traj_condition(
-                curr_gripper, goal_gripper, self.gripper_loc_bounds, trajectory_mask, init_noise, Gk, self._use_goal_at_test)
-        B_scene = B
+                curr_gripper, goal_gripper, self.gripper_loc_bounds, trajectory_mask, init_noise, G or 1, self._use_goal_at_test)
         if G is not None:
             if init_noise is not None:
-                init_noise = init_noise.reshape(B * G, Ln, -1)
+                init_noise = init_noise.reshape(B, Ln, -1)
             if step_noise is not None:
-                step_noise = step_noise.reshape(step_noise.shape[0], B * G, Ln, -1)
+                step_noise = step_noise.reshape(step_noise.shape[0], B, Ln, -1)
                 if plan.flip_noise:
                     step_noise = step_noise.flip(0)
-            if not group:
+            if not plan.group:
                 # fallback paths: every scene's inputs G times along the batch axis (after the image encoding, which stays per scene)
                 rep_ = lambda x: None if x is None else x.repeat_interleave(G, 0)
                 tokens, ctx_xyz = [rep_(x) for x in tokens], [rep_(x) for x in ctx_xyz]
                 cg, gg, instruction, trajectory_mask = rep_(cg), rep_(gg), rep_(instruction), rep_(trajectory_mask)
-                B = B * G
-        # start pose at index 0, goal at L - pad - 1 and after (no host sync: index arithmetic on device)
         if not fused_conditioning:
+            # start pose at index 0, goal at L - pad - 1 and after (no host sync: index arithmetic on device)
+            rows = trajectory_mask.shape[0]                 # per scene on the candidate-group path (expanded below), else per trajectory
             ar = torch.arange(Ln, device=dev)[None, :]
             cond_mask = (ar == 0)
-            cond_data = torch.zeros((B, Ln, D), device=dev)
+            cond_data = torch.zeros((rows, Ln, D), device=dev)
             cond_data[:, 0] = cg
             if self._use_goal_at_test:
                 gidx = (Ln - trajectory_mask.sum(1).long() - 1)[:, None]
                 cond_mask = cond_mask | (ar >= gidx)
                 cond_data = torch.where((ar == gidx)[..., None], gg[:, None, :], cond_data)
-            cond_mask_u8 = cond_mask[..., None].expand(B, Ln, D).to(torch.uint8).contiguous()
+            cond_mask_u8 = cond_mask[..., None].expand(rows, Ln, D).to(torch.uint8).contiguous()
             cond_data = cond_data.contiguous()
             kmask = trajectory_mask.to(torch.uint8).contiguous()
-        if group:
-            # per trajectory from here on: conditioning, masks, noise, the trajectory itself (scene-major); ctx / instr stay per scene
-            if not fused_conditioning:
+            if plan.group:
+                # per trajectory from here on: conditioning, masks, noise, the trajectory itself (scene-major); ctx / instr stay per scene
                 cond_mask_u8, cond_data, kmask = (x.repeat_interleave(G, 0).contiguous() for x in (cond_mask_u8, cond_data, kmask))
-            B = B * G
         if init_noise is None:
             init_noise = torch.randn((B, Ln, D), device=dev)
         if sched is not None and sched.noise_free:
@@ -1396,159 +1449,154 @@ class DiffusionPlanner(nn.Module):
             if step_noise is None:
                 step_noise = torch.randn((self.n_steps if sched is None else sched.K, B, Ln, D), device=dev)
             step_noise = step_noise.to(dev).float().contiguous()
-        sched_key = None if sched is None else sched.key
-        if G is not None:
-            sched_key = (sched_key, "num_samples", G, "group" if group else "expanded")
-        if fused_conditioning:
-            sched_key = (sched_key, "fused_conditioning")
-        if guide is not None:
-            sched_key = (sched_key, "guide") + guide + (g_margin, g_sh, g_st, scene_mask is not None)
         if not fused_conditioning:
             traj = (init_noise.to(dev).float() + cond_data).contiguous()
+        return _Conditioned(B_scene, B, tokens, ctx_xyz, instruction, cg, gg, trajectory_mask, cond_data, cond_mask_u8, kmask,
+                            step_noise, traj)
 
-        # ---- step-invariant state of the planned path; `static` is what a captured graph refreshes in place
-        if multi:
+    def _sampler_state(self, plan, sched, call, c, pcd_obs, trajectory_mask, scene_mask, fused_conditioning, replay):
+        """The step-invariant state of the planned path -> (state, static, key, gd): static is what a captured graph refreshes in
+        place, key names the graph that serves the call, gd holds what the guide pair reads (None without a guide).  trajectory_mask:
+        the call's own, per scene."""
+        head = self.prediction_head
+        Ln = c.traj.shape[1]
+        # tables of the AdaLN modulation: by timestep (full chain) or by step position (schedule)
+        time_sin = self._time_tables["sin"] if sched is None else sched.time_sin
+        if plan.path == "multi-round":
             # the fine-scale context follows the previous prediction, so nothing but the image encoding is step-invariant: every
             # step evaluates the full head (no K/V cache, no fused kernels)
-            state, static = None, tokens + ctx_xyz + [instruction, cg, gg]
-            tmask = trajectory_mask.bool()
+            state, static = {"tmask": c.trajectory_mask.bool()}, c.tokens + c.ctx_xyz + [c.instruction, c.cg, c.gg]
         else:
-            ctx, cxyz, instr = head.encode_context(tokens[0], ctx_xyz[0], instruction, cg, gg)
+            ctx, cxyz, instr = head.encode_context(c.tokens[0], c.ctx_xyz[0], c.instruction, c.cg, c.gg)
             if plan.path == "op-by-op":
                 state = head.build_kv_cache(ctx, cxyz, instr)
-                static = [c[k] for c in state["ctx"] for k in ("Ks", "Vt")] + \
+                static = [kv[k] for kv in state["ctx"] for k in ("Ks", "Vt")] + \
                     ([state["lang"]["Ks"], state["lang"]["Vt"]] if "lang" in state else [])
             else:
                 # fused kernels (csrc/denoise.hip); the persistent sampler's own state follows below, once the graph key is known
-                state = head.build_fused(ctx, cxyz, instr, kmask, time_sin, Ln, n_cand=G if group else 1)
+                state = head.build_fused(ctx, cxyz, instr, c.kmask, time_sin, Ln, n_cand=call.G if plan.group else 1)
                 static = list(state["tensors"])
-        static = static + ([] if step_noise is None else [step_noise]) + [cond_data, cond_mask_u8, kmask]
+        static = static + ([] if c.step_noise is None else [c.step_noise]) + [c.cond_data, c.cond_mask_u8, c.kmask]
         if sched is not None:
             static = static + [sched.coef_pos, sched.coef_rot]
-        replay = use_graph and not return_trace
-        if guide is not None:
+        gd = None
+        if call.guide is not None:
             # what the guide pair reads: the caller's cloud and masks in place; a captured graph addresses copies the planner owns,
             # refreshed with the other static inputs, so a replay sees this call's cloud and never writes into the caller's tensor
-            g_S = _scene_planar(pcd_obs)
-            g_in = [g_S, _mask_bytes(g_mask)] + ([] if scene_mask is None else [_mask_bytes(scene_mask)])
-            g_bounds = O._c(self.gripper_loc_bounds)
+            g_in = [_scene_planar(pcd_obs), _mask_bytes(trajectory_mask)] + ([] if scene_mask is None else [_mask_bytes(scene_mask)])
+            gd = {"bounds": O._c(self.gripper_loc_bounds)}
             static = static + g_in
-        key = (B, Ln, plan.steps, plan.path, tuple((tuple(t_.shape), t_.dtype) for t_ in static), sched_key)
-        if guide is not None:
-            if replay and (self._graph is None or self._graph["key"] != key):       # this call captures: the copies are made once
+        # the graph key, built here and nowhere else; every option that changes the launches wraps the options before it, so the
+        # last entry of a plain scheduled call is the schedule's own key (the tests read it that way)
+        options = None if sched is None else sched.key
+        if call.G is not None:
+            options = (options, "num_samples", call.G, "group" if plan.group else "expanded")
+        if fused_conditioning:
+            options = (options, "fused_conditioning")
+        if call.guide is not None:
+            options = (options, "guide") + call.guide + (call.margin,) + call.skip + (scene_mask is not None,)
+        key = (c.B, Ln, plan.steps, plan.path, tuple((tuple(t_.shape), t_.dtype) for t_ in static), options)
+        captured = replay and self._graph is not None and self._graph["key"] == key
+        if call.guide is not None:
+            if replay and not captured:                     # this call captures: the copies are made once
                 g_in = [t_.clone() for t_ in g_in]
                 static[-len(g_in):] = g_in
-            g_S, g_tm, g_sm = g_in[0], g_in[1], (g_in[2] if len(g_in) > 2 else None)
+            gd["S"], gd["tm"], gd["sm"] = g_in[0], g_in[1], (g_in[2] if len(g_in) > 2 else None)
         if plan.path == "persistent":
             # a replay of the captured loop addresses the state retained in self._graph: no second set of persistent-sampler buffers
             # (a ctypes table, a pageable host-to-device copy = a host sync, five allocations) that would be thrown away
-            gr = self._graph
-            state["persist"] = gr["state"]["persist"] if (replay and gr is not None and gr["key"] == key) else \
-                head._build_persist(state, B, Ln, time_sin.shape[0], group)
-        if group and state.get("persist") is None:
+            state["persist"] = self._graph["state"]["persist"] if captured else \
+                head._build_persist(state, c.B, Ln, time_sin.shape[0], plan.group)
+        if plan.group and state.get("persist") is None:
             raise RuntimeError("num_samples: the per-scene cache was built for a3d_dn_persist_group, which cannot serve this call")
-        if G is not None:
-            self._last_state = state                        # tests read the leading dimensions of the cache
-        self.last_sampler_path = plan.label                 # which sampler serves this call (read by the bench line and the tests)
-        trace = []
+        return state, static, key, gd
 
+    def _guide_step(self, x, last, call, c, gd):
+        """The guide pair on x, the tensor a step just produced (every path returns a new one): updated in place, stream-ordered.
+        last: the step was the final one -- the distances found before the push are kept as gd["nearest"]."""
+        G, Ln = call.G, x.shape[1]
+        if "ws" not in gd:
+            gd["ws"] = torch.empty((O.L.load().a3d_traj_guide_ws_floats(c.B_scene, G or 1, Ln, call.cams * call.pix, 0),),
+                                   device=x.device, dtype=torch.float32)
+        nearest = torch.empty((c.B_scene, G, Ln) if G is not None else (c.B_scene, Ln), device=x.device, dtype=torch.float32) \
+            if last else None
+        _guide_launch(x, gd["tm"], c.cond_mask_u8, gd["bounds"], gd["S"], gd["sm"], call.cams, call.pix, call.margin, call.skip[0],
+                      call.skip[1], call.guide[0], call.guide[1], nearest, gd["ws"], c.B_scene, G or 1, Ln)
+        if last:
+            gd["nearest"] = nearest
+
+    def _run_steps(self, x, plan, tables, call, c, state, gd, segments, trace):
+        """The planned steps on the trajectory batch x, segment by segment (guided_segments: the steps at positions first ..
+        first + count - 1 of plan.steps; guided (count = 1): then the guide pair).  tables: the DDPM-step tables, by timestep
+        (DDPMTables, full chain) or by step position (SamplerSchedule).  trace: the list every step's result is appended to, or
+        None.  This is what a captured graph records."""
+        head = self.prediction_head
         n_exec = len(plan.steps)
-        segments = guided_segments(n_exec, None if guide is None else guide[2])
-        g_out = {}
-
-        def guide_step(x, last):
-            # x is the tensor the step just produced (every path returns a new one): updated in place, stream-ordered
-            if "ws" not in g_out:
-                g_out["ws"] = torch.empty((O.L.load().a3d_traj_guide_ws_floats(B_scene, G or 1, Ln, g_cam * g_pix, 0),), device=dev,
-                                          dtype=torch.float32)
-            nearest = torch.empty((B_scene, G, Ln) if G is not None else (B_scene, Ln), device=dev, dtype=torch.float32) if last else None
-            _guide_launch(x, g_tm, cond_mask_u8, g_bounds, g_S, g_sm, g_cam, g_pix, g_margin, g_sh, g_st, guide[0], guide[1], nearest,
-                          g_out["ws"], B_scene, G or 1, Ln)
-            if last:
-                g_out["nearest"] = nearest
-
-        def run(x):
-            g_out.pop("ws", None)                           # a workspace per run: a captured one belongs to the graph's pool
-            for first, count, guided in segments:
-                x = run_steps(x, first, count, guided)
-            return x
-
-        def run_steps(x, first, count, guided):
-            """the steps at positions first .. first + count - 1 of plan.steps; guided (count = 1): then the guide pair"""
-            if plan.path == "persistent" and not return_trace:      # the whole run of steps: one launch
-                x = head.fused_persist(state, x, first if plan.scheduled else plan.steps[first], count, step_noise, cond_data,
-                                       cond_mask_u8, tables)
+        if gd is not None:
+            gd.pop("ws", None)                              # a workspace per run: a captured one belongs to the graph's pool
+        for first, count, guided in segments:
+            if plan.path == "persistent" and trace is None:         # the whole run of steps: one launch
+                x = head.fused_persist(state, x, first if plan.scheduled else plan.steps[first], count, c.step_noise, c.cond_data,
+                                       c.cond_mask_u8, tables)
                 if guided:
-                    guide_step(x, first == n_exec - 1)
-                return x
+                    self._guide_step(x, first == n_exec - 1, call, c, gd)
+                continue
             for i in range(first, first + count):
                 t = plan.steps[i]
                 # a schedule addresses its tables and its noise by step POSITION and names its terminal step (timestep 0, position
                 # K - 1); the full chain addresses them by timestep.  No step at timestep 0 reads noise.
                 row, term = (i, t == 0) if plan.scheduled else (t, None)
-                nz = None if (step_noise is None or t == 0) else step_noise[row]
+                nz = None if (c.step_noise is None or t == 0) else c.step_noise[row]
                 if plan.path == "persistent":               # traced: the same kernel, one step per launch
-                    x = head.fused_persist(state, x, row, 1, step_noise, cond_data, cond_mask_u8, tables)
+                    x = head.fused_persist(state, x, row, 1, c.step_noise, c.cond_data, c.cond_mask_u8, tables)
                 elif plan.path == "per-phase":
-                    x = head.fused_step(state, x, row, nz, cond_data, cond_mask_u8, tables)
+                    x = head.fused_step(state, x, row, nz, c.cond_data, c.cond_mask_u8, tables)
                 else:
-                    if multi:
-                        tt = torch.full((B,), t, device=dev, dtype=torch.long)
-                        out = head.forward_multi(x, tmask, tt, tokens, ctx_xyz, instruction, cg, gg)[-1]
+                    if plan.path == "multi-round":
+                        tt = torch.full((c.B,), t, device=x.device, dtype=torch.long)
+                        out = head.forward_multi(x, state["tmask"], tt, c.tokens, c.ctx_xyz, c.instruction, c.cg, c.gg)[-1]
                     else:
-                        out = head.denoise_tokens_cached(x, kmask, t, state, self._time_tables)
+                        out = head.denoise_tokens_cached(x, c.kmask, t, state, self._time_tables)
                     if term is None:
-                        x = O.ddpm_step(out, x, nz, cond_data, cond_mask_u8, tables.coef_pos, tables.coef_rot, row)
+                        x = O.ddpm_step(out, x, nz, c.cond_data, c.cond_mask_u8, tables.coef_pos, tables.coef_rot, row)
                     else:
-                        x = O.ddpm_step_sched(out, x, nz, cond_data, cond_mask_u8, tables.coef_pos, tables.coef_rot, row, term)
+                        x = O.ddpm_step_sched(out, x, nz, c.cond_data, c.cond_mask_u8, tables.coef_pos, tables.coef_rot, row, term)
                 if guided:
-                    guide_step(x, i == n_exec - 1)
-                if return_trace:
+                    self._guide_step(x, i == n_exec - 1, call, c, gd)
+                if trace is not None:
                     trace.append(x)
-            return x
+        return x
 
-        traj = self._replay(key, run, traj, static, state) if replay else run(traj)
+    def _finish(self, call, c, traj, trace, gd, segments, replay, trajectory_mask, pcd_obs, goal_gripper, select, rot_weight,
+                scene_mask, clear_margin, clear_skip):
+        """last_guidance, poses, the candidate axis, ranking (last_ranking) -> compute_trajectory's result.  trajectory_mask,
+        pcd_obs (the caller's tensor, in world coordinates) and goal_gripper are the call's own, per scene."""
+        G, Ln = call.G, traj.shape[1]
         self.last_guidance = None
-        if guide is not None:
-            nearest = g_out.get("nearest")
+        if gd is not None:
+            nearest = gd.get("nearest")
             if replay:
                 # the captured guide pair writes the tensor of the capturing call: kept with the graph, handed out as a copy
                 nearest = self._graph.setdefault("guide_nearest", nearest).clone()
             self.last_guidance = Guidance(tuple(i for i, _, guided in segments if guided), nearest)
-
-        # ---- poses, candidates, ranking
         final = signal_to_pose(traj, self.gripper_loc_bounds)
         if G is not None:
-            final = final.reshape(B_scene, G, Ln, final.shape[-1])
-            trace = [x.reshape(B_scene, G, Ln, x.shape[-1]) for x in trace]
+            final = final.reshape(c.B_scene, G, Ln, final.shape[-1])
+            if trace is not None:
+                trace = [x.reshape(c.B_scene, G, Ln, x.shape[-1]) for x in trace]
         if select is not None:
-            rk = rank_trajectories(final, rank_mask, rank_goal, self.gripper_loc_bounds, select, rot_weight, scene=rank_scene,
+            rk = rank_trajectories(final, trajectory_mask, goal_gripper, self.gripper_loc_bounds, select, rot_weight, scene=pcd_obs,
                                    scene_mask=scene_mask, margin=clear_margin, skip=clear_skip)
             self.last_ranking = (ScenePlannerRanking if len(rk) == 7 else PlannerRanking)(*rk, candidates=final)
             final = rk.selected
-        return (final, trace) if return_trace else final
+        return final if trace is None else (final, trace)
 
     def _replay(self, key, run, traj, static, state):
-        """run(traj) through a captured graph: captured on the first call with this key (shapes, steps, path, schedule), afterwards
-        the captured buffers are refreshed in place and the graph is replayed."""
-        if self._graph is None or self._graph["key"] != key:
+        """run(traj) through the planner's captured graph (_graph_replay): "in" is the captured start trajectory, "state" keeps every
+        buffer the captured launches address alive (workspaces, the persistent sampler's tables)."""
+        def capture():
             static_in = traj.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                run(static_in)                              # warm-up (allocator, lazy module state) outside capture
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            # "state" keeps every buffer the captured launches address alive (workspaces, the persistent sampler's tables)
-            self._graph = {"key": key, "in": static_in, "static": static, "state": state}
-            with torch.cuda.graph(g):
-                self._graph["out"] = run(static_in)
-            self._graph["g"] = g
-        gr = self._graph
-        # refresh the captured buffers in place (same addresses; the key pins every shape and dtype)
-        gr["in"].copy_(traj)
-        for dst, src in zip(gr["static"], static):
-            if dst is not src:
-                dst.copy_(src)
-        gr["g"].replay()
-        return gr["out"]
+            return (lambda: run(static_in)), {"in": static_in, "static": static, "state": state}, None
+
+        self._graph = _graph_replay(self._graph, key, capture, [traj] + static, lambda gr: [gr["in"]] + gr["static"])
+        return self._graph["out"]

@@ -133,30 +133,39 @@ class ParallelAttentionLayer(nn.Module):
         self.norm_122 = nn.LayerNorm(d_model)
 
     def forward(self, seq1, seq1_key_padding_mask, seq2, seq1_xyz=None, seq2_xyz=None, seq1_sem_pos=None, silu_t=None,
-                drop=None):
+                drop=None, cross_cache=None):
         """drop: ops.DropCtx of this forward pass (None: no dropout).  Training with dropout_p > 0 needs one -- the owner
-        (DiffusionHead.begin_dropout) creates it; there is no silent un-regularised path."""
-        if self.training and self.dropout_p > 0 and drop is None:
+        (DiffusionHead.begin_dropout) creates it; there is no silent un-regularised path.
+        cross_cache: this layer's prebuilt K/V operands (ops.kv_cache_build): the cross-attention block reads them instead of
+        projecting seq2, which is then unused (inference against the step-invariant context: no autograd, no dropout)."""
+        cached = cross_cache is not None
+        if self.training and self.dropout_p > 0 and drop is None and not cached:
             raise RuntimeError("ParallelAttentionLayer in training mode with dropout=%g needs the forward pass's DropCtx "
                                "(DiffusionHead.begin_dropout())" % self.dropout_p)
-        if drop is not None and (not self.training or self.dropout_p <= 0):
+        if drop is not None and (cached or not self.training or self.dropout_p <= 0):
             drop = None
         sb = self.site_base
         rope = self.rotary_pe
         q1 = seq1 if seq1_sem_pos is None else O.AddRowsFn.apply(seq1, seq1_sem_pos)
         qa = self.adaln_12(q1, silu_t) if (self.adaln_12 is not None and silu_t is not None) else q1
-        # (seq2 may carry a shared gradient sink -- DiffusionHead.forward_tokens attaches one to the context all its cross-attention
-        # layers read: their k | v projection gradients are then parked and run as ONE input- and ONE weight-gradient GEMM)
-        seq1 = O.attn_block(qa, seq2, seq2, seq1, seq1_xyz if rope else None, seq2_xyz if rope else None, None,
-                            self.cross_12, self.norm_12, self.n_heads, drop=drop, site=sb, sink=getattr(seq2, "_a3d_sink", None))
+        if cached:
+            seq1 = O.attn_block_cached(qa, seq1, seq1_xyz if rope else None, cross_cache, self.cross_12, self.norm_12, self.n_heads)
+        else:
+            # (seq2 may carry a shared gradient sink -- DiffusionHead.forward_tokens attaches one to the context all its
+            # cross-attention layers read: their k | v projection gradients are then parked and run as ONE input- and ONE
+            # weight-gradient GEMM)
+            seq1 = O.attn_block(qa, seq2, seq2, seq1, seq1_xyz if rope else None, seq2_xyz if rope else None, None,
+                                self.cross_12, self.norm_12, self.n_heads, drop=drop, site=sb, sink=getattr(seq2, "_a3d_sink", None))
         if self.self_attention1:
             q1 = seq1 if seq1_sem_pos is None else O.AddRowsFn.apply(seq1, seq1_sem_pos)
             if self.adaln_1 is not None and silu_t is not None:
                 qk, vv = self.adaln_1(q1, silu_t), self.adaln_1(seq1, silu_t)
             else:
                 qk, vv = q1, seq1
+            # (the fp16 attention core takes the site as a launch argument even where nothing is dropped: the cached walk keeps
+            # handing it the 0 it always has)
             seq1 = O.attn_block(qk, qk, vv, seq1, seq1_xyz if rope else None, seq1_xyz if rope else None,
-                                seq1_key_padding_mask, self.sa1, self.norm_1, self.n_heads, drop=drop, site=sb + 2)
+                                seq1_key_padding_mask, self.sa1, self.norm_1, self.n_heads, drop=drop, site=0 if cached else sb + 2)
         if self.apply_ffn:
             y = self.adaln_ff1(seq1, silu_t) if (self.adaln_ff1 is not None and silu_t is not None) else seq1
             seq1 = O.mlp(y, self.ffn_12[0], self.ffn_12[3], self.norm_122, drop=drop, site_hidden=sb + 4, site_out=sb + 5)
@@ -168,9 +177,10 @@ class ParallelAttention(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList([ParallelAttentionLayer(**kw) for _ in range(num_layers)])
 
-    def forward(self, seq1, seq1_key_padding_mask, seq2, **kw):
-        for layer in self.layers:
-            seq1 = layer(seq1, seq1_key_padding_mask, seq2, **kw)
+    def forward(self, seq1, seq1_key_padding_mask, seq2, cross_caches=None, **kw):
+        """cross_caches: one K/V cache per layer, in layer order (ParallelAttentionLayer.forward's cross_cache)."""
+        for i, layer in enumerate(self.layers):
+            seq1 = layer(seq1, seq1_key_padding_mask, seq2, cross_cache=None if cross_caches is None else cross_caches[i], **kw)
         return seq1
 
 
