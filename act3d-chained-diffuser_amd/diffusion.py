@@ -853,9 +853,18 @@ class DiffusionHead(nn.Module):
             # and formatting in ONE launch per layer (rounds 2 - 5: a [B S, 2E] fp32 projection in HBM + two formatting passes)
             Kf = torch.empty((B, H, Sp, 32), device=dev, dtype=torch.float16)
             Vt = torch.empty((B, H, 2, 16, Sp), device=dev, dtype=torch.float16)
-            O.L.call("a3d_proj_rope_split16", ctx.data_ptr(), E, mha.in_proj_weight.data_ptr() + E * E * f4, E,
-                     mha.in_proj_bias.data_ptr() + E * f4, E, xyz.data_ptr(), 1.0, Kf.data_ptr(), None, 2,
-                     None, 1.0, None, Vt.data_ptr(), 2 | 4, freq.data_ptr(), B, S, Sp, E, H, O.L.stream())
+            wk, bk = mha.in_proj_weight.data_ptr() + E * E * f4, mha.in_proj_bias.data_ptr() + E * f4
+            if O._fused_proj(E):
+                O.L.call("a3d_proj_rope_split16", ctx.data_ptr(), E, wk, E, bk, E, xyz.data_ptr(), 1.0, Kf.data_ptr(), None, 2,
+                         None, 1.0, None, Vt.data_ptr(), 2 | 4, freq.data_ptr(), B, S, Sp, E, H, O.L.stream())
+            else:
+                # E = 30 / 90 (E % 4 != 0): the fused writer reads rows of X and W as float4 and refuses them; the rule of the op-by-op
+                # path (ops.write_operands): one linear launch for k | v, then one formatting launch per operand
+                kv = O.linear_raw(ctx.data_ptr(), E, wk, E, bk, B * S, 2 * E, E, dev)
+                O.L.call("a3d_rope_split16", kv.data_ptr(), 2 * E, xyz.data_ptr(), freq.data_ptr(), 1.0, Kf.data_ptr(), None, 2,
+                         B, S, Sp, E, H, O.L.stream())
+                O.L.call("a3d_rope_split16", kv.data_ptr() + E * f4, 2 * E, None, freq.data_ptr(), 1.0, None, Vt.data_ptr(), 2 | 4,
+                         B, S, Sp, E, H, O.L.stream())
             mods = [O.linear2d(silu, a.modulation[1].weight, a.modulation[1].bias) for a in (lay.adaln_12, lay.adaln_1, lay.adaln_ff1)]
             st["layers"].append({"lay": lay, "Kf": Kf, "Vt": Vt, "mods": mods})
             st["tensors"] += [Kf, Vt] + mods

@@ -188,9 +188,11 @@ def row_exponent(dO):
     return torch.where(mx > 0, e.to(torch.int64), torch.full_like(e, -1000, dtype=torch.int64))
 
 
-def bounds(ref, q, k, v, kmask, dO=None):
+def bounds(ref, q, k, v, kmask, dO=None, extra_score_err=None):
     """Component-wise bounds from the float64 reference quantities (module docstring).  Returns a namespace with O, O_adaptive, LSE2,
-    LSE2_adaptive and, with dO, dQ, dK, dV, plus dK_dropped / dV_dropped (the DROP_SPAN allowance, zero where nothing may be dropped)."""
+    LSE2_adaptive and, with dO, dQ, dK, dV, plus dK_dropped / dV_dropped (the DROP_SPAN allowance, zero where nothing may be dropped).
+    extra_score_err [B,H,Lq,S] (log2 units, default none): added to eps_s -- the error of a q the kernel under test computes ITSELF
+    instead of being handed as an operand (tests/denoise_ref.py: the cross attention of csrc/denoise.hip)."""
     B, H, Lq, _ = q.shape
     S = k.shape[2]
     w, o = ref.w, ref.O
@@ -199,6 +201,8 @@ def bounds(ref, q, k, v, kmask, dO=None):
     s_abs = torch.where(torch.isinf(ref.s), torch.zeros_like(ref.s), ref.s.abs()).amax(-1, keepdim=True)
     A = q.abs() @ k.abs().transpose(-1, -2) + s_abs + P_OFF + P_THR
     eps_s = C_DOT * U32 * A
+    if extra_score_err is not None:
+        eps_s = eps_s + extra_score_err
     rho = GAMMA_F + LN2 * eps_s
     alive = (~dead).to(F64)
     acc = U32 * n_acc(S) * (w @ v.abs() + o.abs())

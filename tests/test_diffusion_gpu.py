@@ -200,6 +200,59 @@ def test_persistent_sampler_equals_per_phase_launches(a3d, dev, B, Ln, n_steps):
     scale_close("persistent traced vs one launch", got_t, got, 1e-6)
 
 
+@pytest.mark.parametrize("E,H,Ln", [(60, 4, 16), (30, 2, 16), (90, 6, 16), (60, 4, 20)])
+def test_other_head_counts_three_paths_agree(a3d, dev, E, H, Ln):
+    """Head counts no trained weights exist for (H = 4, 2, 6: the persistent sampler splits a unit's keys over nsub = 8 / H = 2, 4, 1
+    waves per head; E = 30 / 90 take the scalar weight loader of the dense layers) on a randomly initialised planner, B = 3, 6 steps:
+    the persistent sampler, the per-phase launches and the op-by-op path agree state by state at the tolerances this file uses for
+    E = 120 (2e-5 fused against op-by-op, 5e-5 persistent against per-phase), the abort word stays zero and a second persistent launch
+    gives the same bits.  Ln = 20 is two row tiles: the per-phase kernels serve one tile only, so the persistent sampler is held against
+    the op-by-op path alone."""
+    B, ncam, n_steps = 3, 2, 6
+    torch.manual_seed(1000 + E + Ln)
+    m = a3d.DiffusionPlanner(embedding_dim=E, num_attn_heads=H, output_dim=7, num_vis_ins_attn_layers=2, num_query_cross_attn_layers=6,
+                             use_instruction=True, use_goal=True, use_goal_at_test=True, weight_tying=True,
+                             gripper_loc_bounds=C.DIFFUSION_BOUNDS, rotation_parametrization="6D", diffusion_timesteps=100)
+    m.to(dev).eval()
+    inp = C.trajectory_inputs(95, B, Ln, ncam, E, pad_last=3)
+    tokens = C.tokens_from_maps(inp["fmap"]).to(dev)
+    d = {k: v.to(dev) for k, v in inp.items()}
+    D = a3d.diffusion
+    assert a3d.lib.load().a3d_dn_persist_splits(H, 1) == (8 // H if 8 % H == 0 else 1)
+
+    def run(persist, **kw):
+        keep = D.DN_PERSIST
+        D.DN_PERSIST = persist
+        head = m.prediction_head
+        head._last_persist = None
+        try:
+            out = m.compute_trajectory(d["mask"], None, d["pcd"], d["instr"], d["curr_gripper"], d["goal_gripper"], init_noise=d["init_noise"],
+                                       step_noise=d["step_noise"], visual_tokens=tokens, n_steps=n_steps, **kw)
+            torch.cuda.synchronize()
+            if persist and kw.get("fused", True):
+                ps = head._last_persist
+                assert ps is not None and int(ps["sync"][2].item()) == 0, "not on the persistent sampler / it gave up waiting"
+            return out
+        finally:
+            D.DN_PERSIST = keep
+
+    tag = f"E={E} H={H} Ln={Ln}"
+    _, t_ops = run(False, fused=False, return_trace=True)
+    got = run(True)
+    assert torch.isfinite(got).all()
+    assert torch.equal(run(True), got), "the persistent sampler is not run-to-run deterministic"
+    got_t, t_pers = run(True, return_trace=True)
+    scale_close(f"{tag}: persistent traced vs one launch", got_t, got, 1e-6)
+    if Ln <= 16:
+        _, t_phase = run(False, return_trace=True)
+        for i in range(n_steps):
+            scale_close(f"{tag}: per-phase fused vs op-by-op state after step {i}", t_phase[i], t_ops[i], 2e-5)
+            scale_close(f"{tag}: persistent vs per-phase state after step {i}", t_pers[i], t_phase[i], 5e-5)
+    else:
+        for i in range(n_steps):
+            scale_close(f"{tag}: persistent (two row tiles) vs op-by-op state after step {i}", t_pers[i], t_ops[i], 2e-5)
+
+
 def test_cfg4_trajectory_half_per_gpu_shape_vs_oracle(a3d, dev):
     """BASELINE.json configs[3] (joint keypose + trajectory-diffusion training, DP batch 128 over 8 GPUs), trajectory half at its
     PER-GPU shape: 16 trajectories of horizon 50 (scripts/train_trajectory.sh), 3 cameras (S = 3074), E = 120 -- training loss and
