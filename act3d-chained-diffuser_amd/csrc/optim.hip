@@ -11,10 +11,15 @@
 //   a3d_adamw_clip_step : a norm launch in front of the same two: sum g^2 in double -> one partial per workgroup; the prepare launch
 //                         combines the partials, decides {skip, clip coefficient} on the device and leaves the effective gradient
 //                         scale in clip_state[0], which the update launch reads in place of the host's grad_scale.  EMA optional.
+//   a3d_adamw_sched_step: any of the above with the learning rate taken from a warm-up + decay schedule that is evaluated on the
+//                         device: the prepare launch derives lr_t from the position and the base rate in lr_state and leaves it
+//                         in lr_state[0], the update launch reads it there and advances the position.  Nothing rate-dependent
+//                         is a kernel argument, so a captured graph follows the schedule and a changed base rate.
 //   a3d_swap_f32        : a <-> b in one pass.
 #include "a3d_common.h"
 #include "../../include/act3d_hip.h"
 #include <algorithm>
+#include <cmath>
 
 namespace a3d {
 
@@ -28,10 +33,11 @@ namespace a3d {
 // is in) advances the step counts and leaves the coefficients for adamw_kernel, whose threads find their element's parameter
 // by bisection of the LDS-staged offsets.  Elements [0, n_nodecay) use weight decay wd0, the rest wd1.
 //
-// ONE prepare kernel and ONE update kernel serve the three entries: <EMA, CLIP> only add statements (if constexpr), so the
+// ONE prepare kernel and ONE update kernel serve the four entries: <EMA, CLIP, SCHED> only add statements (if constexpr), so the
 // arithmetic of p, m, v, step and seg_state is the same expression sequence everywhere -- a3d_adamw_ema_step leaves them bit for bit
-// as a3d_adamw_step does, and a3d_adamw_clip_step as either of them called with grad_scale = clip_state[0] (tests/test_ema_gpu.py,
-// tests/test_grad_clip_gpu.py compare the entries after every step).
+// as a3d_adamw_step does, a3d_adamw_clip_step as either of them called with grad_scale = clip_state[0], and a3d_adamw_sched_step
+// as any of the three called with lr = lr_state[0] (tests/test_ema_gpu.py, tests/test_grad_clip_gpu.py, tests/test_lr_schedule_gpu.py
+// compare the entries after every step).
 constexpr int ADAMW_LDS_SEGS = 4096;
 constexpr int CLIP_PARTS = A3D_ADAMW_CLIP_WS_DOUBLES;       // workgroups of the norm pass = partials in clip_ws
 static_assert(CLIP_PARTS == 256, "clip_decide reads one partial per thread of a 256-thread workgroup");
@@ -89,18 +95,44 @@ __device__ __forceinline__ ClipDecision clip_decide(const double* __restrict__ p
   return d;
 }
 
+// The rate of a scheduled step (tests/lr_schedule_ref.py is the float64 statement): t = lr_state[1] scheduled steps applied so
+// far, base = lr_state[3];
+//   t < W: f = t / W;   else constant: f = 1;   linear: f = 1 - (1 - r) u;   cosine: f = r + (1 - r) (1 + cos(pi u)) / 2
+//   u = min(1, (t - W) / (N - W));   lr_t = fp32(base f), everything before that rounding in double.
+// Derived by one thread of every prepare workgroup from the same two words with the same code, hence with the same bits.
+struct SchedArgs {
+  double warmup, total, min_ratio;
+  int kind;
+};
+struct SchedRate {
+  float lr, f;
+};
+__device__ __forceinline__ SchedRate sched_rate(const float* __restrict__ lr_state, const SchedArgs& sc) {
+  const double t = lr_state[1], base = lr_state[3];
+  double f = 1.0;
+  if (t < sc.warmup) {
+    f = t / sc.warmup;
+  } else if (sc.kind != A3D_LR_CONSTANT) {
+    const double u = fmin(1.0, (t - sc.warmup) / (sc.total - sc.warmup)), r = sc.min_ratio;
+    f = sc.kind == A3D_LR_LINEAR ? 1.0 - (1.0 - r) * u : r + (1.0 - r) * (1.0 + cos(3.14159265358979323846 * u)) / 2.0;
+  }
+  return {(float)(base * f), (float)f};
+}
+
 // One workgroup per parameter; the thread that counts the optimizer step also advances the EMA:
 //   t = updates + 1;  w = 1 - min(decay, (1 + t) / (warmup + t)) = max(1 - decay, (warmup - 1) / (warmup + t))      (warmup >= 1)
 //   w = 1 - decay                                                                                                   (warmup == 0)
 // CLIP: every workgroup first derives the decision; workgroup 0 records it in clip_state (the only writer, and nobody reads
 // clip_state in this launch), and on a skip every workgroup leaves before it has written anything.
-template <bool EMA, bool CLIP>
+// SCHED: thread 0 of every workgroup derives the step's rate from lr_state[1] and [3]; workgroup 0 records it in lr_state[0] and
+// [2] (the only writer, and nobody reads those two words in this launch; [1] is advanced by the update launch).
+template <bool EMA, bool CLIP, bool SCHED>
 __global__ __launch_bounds__(256) void adamw_prepare_kernel(const float* __restrict__ g, const long long* __restrict__ seg_off,
                                                             float* __restrict__ seg_state, float* __restrict__ step,
                                                             float* __restrict__ ema_state, float* __restrict__ clip_state,
                                                             const double* __restrict__ clip_ws, int clip_parts, float lr, float beta1,
                                                             float beta2, float ema_decay, float ema_warmup, float gscale,
-                                                            float max_norm) {
+                                                            float max_norm, float* __restrict__ lr_state, SchedArgs sched) {
   const int seg = blockIdx.x;
   if constexpr (CLIP) {
     __shared__ double wsum[4];
@@ -126,6 +158,14 @@ __global__ __launch_bounds__(256) void adamw_prepare_kernel(const float* __restr
     in_graph = __syncthreads_or(nz);
   }
   if (threadIdx.x == 0) {
+    if constexpr (SCHED) {
+      const SchedRate r = sched_rate(lr_state, sched);
+      lr = r.lr;
+      if (seg == 0) {
+        lr_state[0] = r.lr;
+        lr_state[2] = r.f;
+      }
+    }
     if (in_graph) {
       const float t = st[0] + 1.0f;
       st[0] = t;
@@ -150,17 +190,22 @@ __global__ __launch_bounds__(256) void adamw_prepare_kernel(const float* __restr
 
 // EMA: the average is updated from the p the thread has just formed: 5 loads + 4 stores per element instead of the 4 + 3 of the
 // plain step followed by a 2 + 1 lerp launch.  CLIP: the gradient scale is the e the prepare launch left in clip_state[0]; on a
-// skipped step (clip_state[5]) nothing is read or written.
-template <bool EMA, bool CLIP>
+// skipped step (clip_state[5]) nothing is read or written.  SCHED: the rate is the lr_t the prepare launch left in lr_state[0], and
+// one thread counts the applied step in lr_state[1] (its only writer; nobody reads it in this launch).
+template <bool EMA, bool CLIP, bool SCHED>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, float* __restrict__ ema,
                                                     const long long* __restrict__ seg_off, const float* __restrict__ seg_state,
                                                     const float* __restrict__ ema_state, const float* __restrict__ clip_state,
                                                     int nseg, size_t n, size_t n_nodecay, float lr, float beta1, float beta2, float eps,
-                                                    float wd0, float wd1, float gscale) {
+                                                    float wd0, float wd1, float gscale, float* __restrict__ lr_state) {
   if constexpr (CLIP) {
     if (clip_state[5] != 0.0f) return;
     gscale = clip_state[0];
+  }
+  if constexpr (SCHED) {
+    lr = lr_state[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) lr_state[1] += 1.0f;
   }
   __shared__ long long offS[ADAMW_LDS_SEGS + 1];
   const bool staged = nseg <= ADAMW_LDS_SEGS;
@@ -214,7 +259,7 @@ __global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, fl
   }
 }
 
-// The parameters of one step, shared by the three entries (absent parts null / 0).
+// The parameters of one step, shared by the four entries (absent parts null / 0).
 struct AdamWArgs {
   float *p, *m, *v, *ema, *step, *seg_state, *ema_state, *clip_state;
   const float* g;
@@ -223,18 +268,40 @@ struct AdamWArgs {
   int nseg, clip_parts;
   size_t n, n_nodecay;
   float lr, beta1, beta2, eps, wd0, wd1, gscale, ema_decay, ema_warmup, max_norm;
+  float* lr_state = nullptr;
+  SchedArgs sched = {0.0, 0.0, 0.0, A3D_LR_CONSTANT};
 };
 
-template <bool EMA, bool CLIP>
+template <bool EMA, bool CLIP, bool SCHED = false>
 static int launch_adamw(const AdamWArgs& a, hipStream_t s, const char* prepare_name, const char* name) {
-  hipLaunchKernelGGL((adamw_prepare_kernel<EMA, CLIP>), dim3(a.nseg), dim3(256), 0, s, a.g, a.seg_off, a.seg_state, a.step, a.ema_state,
-                     a.clip_state, a.clip_ws, a.clip_parts, a.lr, a.beta1, a.beta2, a.ema_decay, a.ema_warmup, a.gscale, a.max_norm);
+  hipLaunchKernelGGL((adamw_prepare_kernel<EMA, CLIP, SCHED>), dim3(a.nseg), dim3(256), 0, s, a.g, a.seg_off, a.seg_state, a.step, a.ema_state,
+                     a.clip_state, a.clip_ws, a.clip_parts, a.lr, a.beta1, a.beta2, a.ema_decay, a.ema_warmup, a.gscale, a.max_norm,
+                     a.lr_state, a.sched);
   int rc = check_launch(prepare_name);
   if (rc) return rc;
   const int grid = (int)std::min<size_t>((a.n + 255) / 256, 2048);
-  hipLaunchKernelGGL((adamw_kernel<EMA, CLIP>), dim3(grid), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.ema, a.seg_off, a.seg_state, a.ema_state,
-                     a.clip_state, a.nseg, a.n, a.n_nodecay, a.lr, a.beta1, a.beta2, a.eps, a.wd0, a.wd1, a.gscale);
+  hipLaunchKernelGGL((adamw_kernel<EMA, CLIP, SCHED>), dim3(grid), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.ema, a.seg_off, a.seg_state, a.ema_state,
+                     a.clip_state, a.nseg, a.n, a.n_nodecay, a.lr, a.beta1, a.beta2, a.eps, a.wd0, a.wd1, a.gscale, a.lr_state);
   return check_launch(name);
+}
+
+// The norm pass of a clipped step; *parts = the partials it leaves in clip_ws.
+static int launch_grad_sqnorm(const float* g, size_t n, double* clip_ws, hipStream_t s, const char* name, int* parts) {
+  const size_t head = std::min<size_t>(((16u - ((uintptr_t)g & 15u)) & 15u) / 4u, n);
+  const size_t nvec = (n - head) / 4;
+  // always CLIP_PARTS workgroups would leave most of them idle on a small buffer; the idle ones' partials are simply not written and
+  // not read: the prepare launch is told how many there are
+  *parts = (int)std::min<size_t>(std::max<size_t>((nvec + 255) / 256, 1), CLIP_PARTS);
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(*parts), dim3(256), 0, s, g, n, head, nvec, clip_ws);
+  return check_launch(name);
+}
+
+static int check_max_norm(const char* who, float max_norm) {
+  if (!(max_norm > 0.0f)) {                                     // NaN fails the comparison; +inf is legal (measure only)
+    set_error("%s: max_norm = %g must be > 0 (+inf: measure the norm, never clip)", who, (double)max_norm);
+    return A3D_ERR_ARG;
+  }
+  return A3D_OK;
 }
 
 static int check_ema_ranges(const char* who, float ema_decay, float ema_warmup) {
@@ -299,25 +366,73 @@ extern "C" int a3d_adamw_clip_step(float* p, const float* g, float* m, float* v,
     set_error("a3d_adamw_clip_step: the flat buffer needs at least one parameter segment (nseg = %d)", nseg);
     return A3D_ERR_ARG;
   }
-  if (!(max_norm > 0.0f)) {                                     // NaN fails the comparison; +inf is legal (measure only)
-    set_error("a3d_adamw_clip_step: max_norm = %g must be > 0 (+inf: measure the norm, never clip)", (double)max_norm);
-    return A3D_ERR_ARG;
-  }
+  if (check_max_norm("a3d_adamw_clip_step", max_norm)) return A3D_ERR_ARG;
   if (ema && check_ema_ranges("a3d_adamw_clip_step", ema_decay, ema_warmup)) return A3D_ERR_ARG;
   if (n == 0) return A3D_OK;
   hipStream_t s = (hipStream_t)stream;
-  const size_t head = std::min<size_t>(((16u - ((uintptr_t)g & 15u)) & 15u) / 4u, n);
-  const size_t nvec = (n - head) / 4;
-  // always CLIP_PARTS workgroups would leave most of them idle on a small buffer; the idle ones' partials are simply not written and
-  // not read: the prepare launch is told how many there are
-  const int parts = (int)std::min<size_t>(std::max<size_t>((nvec + 255) / 256, 1), CLIP_PARTS);
-  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(parts), dim3(256), 0, s, g, n, head, nvec, clip_ws);
-  int rc = check_launch("a3d_adamw_clip_step(norm)");
+  int parts = 0;
+  int rc = launch_grad_sqnorm(g, n, clip_ws, s, "a3d_adamw_clip_step(norm)", &parts);
   if (rc) return rc;
   const AdamWArgs a = {p, m, v, ema, step, seg_state, ema_state, clip_state, g, seg_off, clip_ws, nseg, parts, n, n_nodecay,
                        lr, beta1, beta2, eps, wd_nodecay, wd_decay, grad_scale, ema_decay, ema_warmup, max_norm};
   return ema ? launch_adamw<true, true>(a, s, "a3d_adamw_clip_step(prepare)", "a3d_adamw_clip_step")
              : launch_adamw<false, true>(a, s, "a3d_adamw_clip_step(prepare)", "a3d_adamw_clip_step");
+}
+
+extern "C" int a3d_adamw_sched_step(float* p, const float* g, float* m, float* v, float* ema, float* step, const long long* seg_off,
+                                    float* seg_state, float* ema_state, float* clip_state, double* clip_ws, float* lr_state, int nseg,
+                                    size_t n, size_t n_nodecay, int decay_kind, double warmup_steps, double total_steps,
+                                    double min_ratio, float beta1, float beta2, float eps, float wd_nodecay, float wd_decay,
+                                    float grad_scale, float ema_decay, float ema_warmup, float max_norm, void* stream) {
+  const char* who = "a3d_adamw_sched_step";
+  if (!p || !g || !m || !v || !step || !seg_off || !seg_state || !lr_state) { set_error("%s: null pointer", who); return A3D_ERR_ARG; }
+  if ((ema == nullptr) != (ema_state == nullptr)) {
+    set_error("%s: ema and ema_state must both be given or both be null", who);
+    return A3D_ERR_ARG;
+  }
+  if ((clip_state == nullptr) != (clip_ws == nullptr)) {
+    set_error("%s: clip_state and clip_ws must both be given or both be null", who);
+    return A3D_ERR_ARG;
+  }
+  if (nseg <= 0) {
+    set_error("%s: the flat buffer needs at least one parameter segment (nseg = %d)", who, nseg);
+    return A3D_ERR_ARG;
+  }
+  if (decay_kind != A3D_LR_CONSTANT && decay_kind != A3D_LR_LINEAR && decay_kind != A3D_LR_COSINE) {
+    set_error("%s: unknown decay_kind %d", who, decay_kind);
+    return A3D_ERR_ARG;
+  }
+  const double limit = 16777216.0;                              // the position is an fp32 counter: exact below 2^24
+  if (!(warmup_steps >= 0.0 && warmup_steps < limit && warmup_steps == std::floor(warmup_steps))) {   // NaN fails the comparisons
+    set_error("%s: warmup_steps = %g must be an integer value in [0, 2^24)", who, warmup_steps);
+    return A3D_ERR_ARG;
+  }
+  if (decay_kind != A3D_LR_CONSTANT &&
+      !(total_steps > warmup_steps && total_steps < limit && total_steps == std::floor(total_steps))) {
+    set_error("%s: total_steps = %g must be an integer value in (warmup_steps = %g, 2^24) for a decaying schedule", who, total_steps,
+              warmup_steps);
+    return A3D_ERR_ARG;
+  }
+  if (!(min_ratio >= 0.0 && min_ratio <= 1.0)) {
+    set_error("%s: min_ratio = %g is outside [0, 1]", who, min_ratio);
+    return A3D_ERR_ARG;
+  }
+  if (clip_state && check_max_norm(who, max_norm)) return A3D_ERR_ARG;
+  if (ema && check_ema_ranges(who, ema_decay, ema_warmup)) return A3D_ERR_ARG;
+  if (n == 0) return A3D_OK;
+  hipStream_t s = (hipStream_t)stream;
+  int parts = 0;
+  if (clip_state) {
+    int rc = launch_grad_sqnorm(g, n, clip_ws, s, "a3d_adamw_sched_step(norm)", &parts);
+    if (rc) return rc;
+  }
+  AdamWArgs a = {p, m, v, ema, step, seg_state, ema_state, clip_state, g, seg_off, clip_ws, nseg, parts, n, n_nodecay,
+                 0.0f, beta1, beta2, eps, wd_nodecay, wd_decay, grad_scale, ema_decay, ema_warmup, max_norm};
+  a.lr_state = lr_state;
+  a.sched = {warmup_steps, total_steps, min_ratio, decay_kind};
+  const char* prep = "a3d_adamw_sched_step(prepare)";
+  if (clip_state) return ema ? launch_adamw<true, true, true>(a, s, prep, who) : launch_adamw<false, true, true>(a, s, prep, who);
+  return ema ? launch_adamw<true, false, true>(a, s, prep, who) : launch_adamw<false, false, true>(a, s, prep, who);
 }
 
 extern "C" int a3d_swap_f32(float* a, float* b, size_t n, void* stream) {

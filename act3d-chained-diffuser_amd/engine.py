@@ -116,6 +116,35 @@ def _check_max_grad_norm(max_grad_norm):
     return x
 
 
+def _check_lr_schedule(lr_schedule):
+    """The schedules a3d_adamw_sched_step accepts, checked where the keyword enters.  A preset name ("constant", "linear",
+    "cosine") or a dict over decay / warmup / total / min_ratio; returns None (off) or the complete dict.  `total` is required
+    unless the rate stays constant after the warm-up."""
+    if lr_schedule is None:
+        return None
+    s = {"decay": lr_schedule} if isinstance(lr_schedule, str) else lr_schedule
+    if not isinstance(s, dict) or not set(s) <= {"decay", "warmup", "total", "min_ratio"}:
+        raise ValueError("lr_schedule = %r: expected a preset name or a dict over decay, warmup, total, min_ratio" % (lr_schedule,))
+    decay, warmup, total, ratio = s.get("decay", "constant"), s.get("warmup", 0), s.get("total"), s.get("min_ratio", 0.0)
+
+    def steps(name, x):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not (0 <= x < 2 ** 24) or x != int(x):
+            raise ValueError("lr_schedule: %s = %r must be an integer in [0, 2^24)" % (name, x))
+        return int(x)
+    if not isinstance(decay, str) or decay not in L.LR_DECAY_KINDS:
+        raise ValueError("lr_schedule: decay = %r (expected one of %s)" % (decay, sorted(L.LR_DECAY_KINDS)))
+    warmup = steps("warmup", warmup)
+    if decay != "constant":
+        if total is None:
+            raise ValueError("lr_schedule: decay = %r needs total, the step at which the decay ends" % (decay,))
+        if steps("total", total) <= warmup:
+            raise ValueError("lr_schedule: total = %r must be above warmup = %r" % (total, warmup))
+    total = None if total is None else steps("total", total)
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not (0.0 <= ratio <= 1.0):      # NaN fails the comparison
+        raise ValueError("lr_schedule: min_ratio = %r is outside [0, 1]" % (ratio,))
+    return {"decay": decay, "warmup": warmup, "total": total, "min_ratio": float(ratio)}
+
+
 class FlatAdamW:
     """torch.optim.AdamW semantics (lr, betas, eps, two weight-decay groups) as one fused kernel over FlatParams.
 
@@ -126,13 +155,24 @@ class FlatAdamW:
 
     With `max_grad_norm` the step clips the global norm of the (grad_scale-averaged) gradient to that value and skips a step whose
     norm is not finite, both decided on the device inside the same call: `grad_norm`, `clip_scale`, `clipped_steps`,
-    `skipped_steps`, `last_step_skipped` are views of the device state.  That state is not part of state_dict() / checkpoints."""
+    `skipped_steps`, `last_step_skipped` are views of the device state.  That state is not part of state_dict() / checkpoints.
+
+    With `lr_schedule` the rate of every step is `lr` times a warm-up + decay factor that the step evaluates on the device from
+    its own position, so a captured step graph follows the schedule and a later `optimizer.lr = x`: `current_lr`,
+    `lr_factor` and `schedule_step` are views of the device state.  `lr` and the checkpoints keep the base rate; a loaded state
+    continues the schedule at its step count."""
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-4, ema_decay=None, ema_warmup=10,
-                 max_grad_norm=None):
+                 max_grad_norm=None, lr_schedule=None):
         self.flat, self.betas, self.eps, self.weight_decay = flat, betas, eps, weight_decay
         self.ema_decay, self.ema_warmup = _check_ema(ema_decay, ema_warmup)
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.lr_schedule = _check_lr_schedule(lr_schedule)
+        self.lr_state = None
+        if self.lr_schedule is not None:
+            # {lr_t of the last applied step, position t, f(t) of the last applied step, base rate, 0, 0, 0, 0}
+            self.lr_state = torch.zeros(8, device=flat.flat.device, dtype=torch.float32)
+            self.lr_state[3] = float(lr)
         self.clip_state = self.clip_ws = None
         if self.max_grad_norm is not None:
             # {e applied, norm, coef, clipped steps, skipped steps, last step skipped, 0, 0} and the norm pass's partials
@@ -163,6 +203,8 @@ class FlatAdamW:
     def lr(self, value):
         for g in self.param_groups:
             g["lr"] = float(value)
+        if self.lr_state is not None:            # the base rate of the device schedule: stream-ordered, reaches every later replay
+            self.lr_state[3] = float(value)
 
     def zero_grad(self, set_to_none=False):
         self.flat.zero_grad()
@@ -172,6 +214,17 @@ class FlatAdamW:
         if self.ema is not None and self.ema_swapped:
             raise RuntimeError("FlatAdamW.step() while the EMA weights are swapped in: it would train the averages "
                                "(leave ema_weights() / call swap_ema() first)")
+        if self.lr_state is not None:
+            has_ema, clips, sc = self.ema is not None, self.clip_state is not None, self.lr_schedule
+            L.call("a3d_adamw_sched_step", f.flat.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
+                   self.exp_avg_sq.data_ptr(), self.ema.data_ptr() if has_ema else None, self.step_count.data_ptr(),
+                   self.seg_off.data_ptr(), self.seg_state.data_ptr(), self.ema_state.data_ptr() if has_ema else None,
+                   self.clip_state.data_ptr() if clips else None, self.clip_ws.data_ptr() if clips else None,
+                   self.lr_state.data_ptr(), len(f.order), f.n, f.n_nodecay, L.LR_DECAY_KINDS[sc["decay"]], float(sc["warmup"]),
+                   float(sc["total"] or 0), sc["min_ratio"], self.betas[0], self.betas[1], self.eps, 0.0,
+                   float(self.weight_decay), float(grad_scale), self.ema_decay if has_ema else 0.0,
+                   self.ema_warmup if has_ema else 0.0, self.max_grad_norm if clips else 0.0, L.stream())
+            return
         if self.clip_state is not None:
             has_ema = self.ema is not None
             L.call("a3d_adamw_clip_step", f.flat.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
@@ -205,6 +258,33 @@ class FlatAdamW:
             self.reset_ema()
         if self.clip_state is not None:
             self.clip_state.zero_()
+        if self.lr_state is not None:
+            self.lr_state[:3].zero_()            # the schedule starts over; the base rate stays
+
+    # ---- learning-rate schedule (lr_schedule is not None): views of the device state, none of them synchronises
+    def _lr_slot(self, what, k):
+        if self.lr_state is None:
+            raise RuntimeError("%s: this optimizer has no learning-rate schedule (built with lr_schedule=None)" % what)
+        return self.lr_state[k]
+
+    @property
+    def current_lr(self):
+        """The rate the last applied step ran at: fp32(lr * lr_factor) (lr_state[0])."""
+        return self._lr_slot("current_lr", 0)
+
+    @property
+    def lr_factor(self):
+        """The schedule's factor f(t) of the last applied step (lr_state[2])."""
+        return self._lr_slot("lr_factor", 2)
+
+    @property
+    def schedule_step(self):
+        """Scheduled steps applied so far = the position t the next step runs at (lr_state[1]); skipped steps do not count."""
+        return self._lr_slot("schedule_step", 1)
+
+    @schedule_step.setter
+    def schedule_step(self, value):
+        self._lr_slot("schedule_step", 1).fill_(float(value))
 
     # ---- gradient-norm clipping (max_grad_norm is not None): views of the device state, none of them synchronises
     def _clip_slot(self, what, k):
@@ -340,19 +420,23 @@ class FlatAdamW:
             self.exp_avg_sq[a:b].copy_(st["exp_avg_sq"].reshape(-1))
         self.seg_state[:, 0].copy_(steps)
         self.step_count.fill_(float(steps.max()) if len(loaded) else 0.0)
+        if self.lr_state is not None:            # the schedule continues where the loaded run stood: no persisted state of its own
+            self.schedule_step = float(steps.max()) if len(loaded) else 0.0
         self.lr = sd["param_groups"][0].get("lr", self.lr)
 
 
-def get_optimizer(model, lr=1e-4, active_names=None, ema_decay=None, ema_warmup=10, max_grad_norm=None):
+def get_optimizer(model, lr=1e-4, active_names=None, ema_decay=None, ema_warmup=10, max_grad_norm=None, lr_schedule=None):
     """engine.py:89-102 on the flat buffers.  Returns (FlatParams, FlatAdamW).  With active_names=None every trainable
     parameter is placed in the buffer; parameters that never receive a gradient are left untouched by the fused AdamW kernel
     (as torch.optim.AdamW skips parameters whose .grad is None -- no weight decay on unused FPN blocks).  ema_decay / ema_warmup:
     FlatAdamW's EMA of the weights (off by default).  max_grad_norm: FlatAdamW's global gradient-norm clipping + non-finite step
-    skip (off by default)."""
+    skip (off by default).  lr_schedule: FlatAdamW's device-resident warm-up + decay of the rate (off by default)."""
     _check_ema(ema_decay, ema_warmup)                # before the parameters are re-homed
     _check_max_grad_norm(max_grad_norm)
+    _check_lr_schedule(lr_schedule)
     flat = FlatParams(model, active_names)
-    return flat, FlatAdamW(flat, lr=lr, ema_decay=ema_decay, ema_warmup=ema_warmup, max_grad_norm=max_grad_norm)
+    return flat, FlatAdamW(flat, lr=lr, ema_decay=ema_decay, ema_warmup=ema_warmup, max_grad_norm=max_grad_norm,
+                           lr_schedule=lr_schedule)
 
 
 DP_ONESHOT = os.environ.get("A3D_DP_ONESHOT", "0") == "1"

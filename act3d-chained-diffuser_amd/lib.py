@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_PKG_DIR, os.path.basename(os.environ.get("A3D_LIB", "li
 _p = C.c_void_p
 _i = C.c_int
 _f = C.c_float
+_d = C.c_double
 _z = C.c_size_t
 _u64 = C.c_ulonglong
 
@@ -162,6 +163,7 @@ SIGNATURES = {
     # optim.hip
     "a3d_adamw_ema_step": (_i, [_p] * 9 + [_i, _z, _z] + [_f] * 9 + [_p]),
     "a3d_adamw_clip_step": (_i, [_p] * 11 + [_i, _z, _z] + [_f] * 10 + [_p]),
+    "a3d_adamw_sched_step": (_i, [_p] * 12 + [_i, _z, _z, _i] + [_d] * 3 + [_f] * 9 + [_p]),
     "a3d_swap_f32": (_i, [_p, _p, _z, _p]),
     "a3d_dbg_mfma_bf16": (_i, [_p, _p, _p, _p]),
     "a3d_dbg_mfma_f32": (_i, [_p, _p, _p, _p]),
@@ -209,6 +211,8 @@ SIGNATURES = {
 
 # doubles in a3d_adamw_clip_step's clip_ws = workgroups of its norm pass (A3D_ADAMW_CLIP_WS_DOUBLES in the header)
 ADAMW_CLIP_WS_DOUBLES = 256
+# a3d_adamw_sched_step's decay_kind (A3D_LR_* in the header)
+LR_DECAY_KINDS = {"constant": 0, "linear": 1, "cosine": 2}
 
 _lib = None
 

@@ -223,6 +223,19 @@ def _seed_worker(worker_id):
 
 
 # ------------------------------------------------------------------------------------------------ drivers
+def _lr_schedule(a):
+    """FlatAdamW's lr_schedule from args.lr_schedule (absent, None or "": a constant rate, no schedule), args.lr_warmup,
+    args.lr_min_ratio and args.lr_total, which defaults to the optimizer steps of the run: ceil(train_iters /
+    accumulate_grad_batches)."""
+    decay = getattr(a, "lr_schedule", None) or None
+    if decay is None:
+        return None
+    total = getattr(a, "lr_total", None)
+    if total is None and decay != "constant":
+        total = -(-int(a.train_iters) // max(1, int(getattr(a, "accumulate_grad_batches", 1))))
+    return {"decay": decay, "warmup": getattr(a, "lr_warmup", 0), "total": total, "min_ratio": getattr(a, "lr_min_ratio", 0.0)}
+
+
 class BaseTrainTester:
     """The driver skeleton.  Subclasses say what the datasets, the model, the criterion, one training step and one
     evaluation round are; `main` wires loaders -> model -> optimizer -> (DP) -> resume -> the scheduled loop."""
@@ -279,7 +292,8 @@ class BaseTrainTester:
         """The reference's two AdamW groups (engine.py:89-102) as ONE fused optimizer over flat buffers (`optimizer.flat`)."""
         return E.get_optimizer(model, lr=self.args.lr, ema_decay=getattr(self.args, "ema_decay", None) or None,
                                ema_warmup=getattr(self.args, "ema_warmup", 10),
-                               max_grad_norm=getattr(self.args, "max_grad_norm", None) or None)[1]
+                               max_grad_norm=getattr(self.args, "max_grad_norm", None) or None,
+                               lr_schedule=_lr_schedule(self.args))[1]
 
     def _eval_weights(self, optimizer):
         """The weights an evaluation reads: the optimizer's EMA (swapped in for the duration) with args.ema_eval (default 1)
@@ -340,7 +354,11 @@ class BaseTrainTester:
 
     def _log_train(self, loss, step_id, optimizer=None):
         if self.writer is not None and (step_id + 1) % self.args.val_freq == 0:
-            self.writer.add_scalar("lr", self.args.lr, step_id)
+            if getattr(optimizer, "lr_state", None) is not None:          # scheduled: the rate of the last step, read only here
+                self.writer.add_scalar("lr", optimizer.current_lr, step_id)
+                self.writer.add_scalar("train-stats/lr_factor", optimizer.lr_factor, step_id)
+            else:
+                self.writer.add_scalar("lr", self.args.lr, step_id)
             self.writer.add_scalar("train-loss/noise_mse", loss, step_id)
             if getattr(optimizer, "clip_state", None) is not None:        # the optimizer clips: its device counters, read only here
                 self.writer.add_scalar("train-stats/grad_norm", optimizer.grad_norm, step_id)
@@ -349,7 +367,8 @@ class BaseTrainTester:
 
     def load_checkpoint(self, model, optimizer):
         """Weights + optimizer state from args.checkpoint; the learning rate is reset to args.lr as the reference does
-        (engine.py:195-212).  Returns (start_iter, best_loss)."""
+        (engine.py:195-212) -- with args.lr_schedule that is the base rate, and the schedule continues at the checkpoint's step
+        count.  Returns (start_iter, best_loss)."""
         start_iter, best_loss = E.load_checkpoint(self.args.checkpoint, model, optimizer)
         optimizer.lr = self.args.lr
         print(f"resumed from {self.args.checkpoint} at step {start_iter}")

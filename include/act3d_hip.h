@@ -401,6 +401,34 @@ int a3d_adamw_clip_step(float* p, const float* g, float* m, float* v, float* ema
                         float* seg_state, float* ema_state, float* clip_state, double* clip_ws, int nseg, size_t n, size_t n_nodecay,
                         float lr, float beta1, float beta2, float eps, float wd_nodecay, float wd_decay, float grad_scale,
                         float ema_decay, float ema_warmup, float max_norm, void* stream);
+/* Any of the three entries above with the learning rate taken from a warm-up + decay schedule that is evaluated on the device
+ * (csrc/optim.hip; the reference trains at a constant rate).  There is no lr argument: nothing rate-dependent is frozen into a
+ * captured graph.  ema / ema_state and clip_state / clip_ws may each be both null or both given: without clip_state this makes the
+ * two launches of a3d_adamw_step / a3d_adamw_ema_step, with it the three of a3d_adamw_clip_step.
+ * With t the number of scheduled steps applied so far (the 0-based index of this step), W = warmup_steps, N = total_steps,
+ * r = min_ratio:
+ *   t <  W                        f = t / W                                  (the first step of a warm-up runs at rate 0)
+ *   t >= W, A3D_LR_CONSTANT       f = 1
+ *   t >= W, A3D_LR_LINEAR         f = 1 - (1 - r) u                          u = min(1, (t - W) / (N - W))
+ *   t >= W, A3D_LR_COSINE         f = r + (1 - r) (1 + cos(pi u)) / 2
+ *   lr_t = fp32(base f), everything before that rounding in double; past N the rate stays at r base (u is clamped).
+ * lr_state [8] (fp32, device, zero-initialised by the caller, who then writes the base rate) = {lr_t of the last applied step, t,
+ * f(t) of the last applied step, base rate, 0, 0, 0, 0}.  The prepare launch reads [1] and [3] and writes [0] and [2]; the update
+ * launch reads [0] and advances [1]; t is a float like the other device counters, exact to 2^24 steps.  p, m, v, step, seg_state,
+ * ema and ema_state end bit for bit what a3d_adamw_step / a3d_adamw_ema_step / a3d_adamw_clip_step leave when called with
+ * lr = lr_state[0].  A step that the clip logic skips writes nothing of lr_state and does not advance t.
+ * -22 for a null pointer (other than the two optional pairs), exactly one of a pair null, nseg <= 0, an unknown decay_kind,
+ * warmup_steps not a non-negative integer value, total_steps not an integer value or <= warmup_steps for a decaying kind (it is not
+ * looked at for A3D_LR_CONSTANT), either of them >= 2^24, min_ratio NaN or outside [0, 1], and the max_norm / ema_decay / ema_warmup
+ * checks of the entries above for the parts that are given.  n == 0 returns 0 after the checks. */
+#define A3D_LR_CONSTANT 0
+#define A3D_LR_LINEAR 1
+#define A3D_LR_COSINE 2
+int a3d_adamw_sched_step(float* p, const float* g, float* m, float* v, float* ema, float* step, const long long* seg_off,
+                         float* seg_state, float* ema_state, float* clip_state, double* clip_ws, float* lr_state, int nseg, size_t n,
+                         size_t n_nodecay, int decay_kind, double warmup_steps, double total_steps, double min_ratio, float beta1,
+                         float beta2, float eps, float wd_nodecay, float wd_decay, float grad_scale, float ema_decay, float ema_warmup,
+                         float max_norm, void* stream);
 /* a[i] <-> b[i] for i < n in one pass (csrc/optim.hip); replaces torch's three-copy exchange through a temporary (tmp = a.clone();
  * a.copy_(b); b.copy_(tmp)).  Any n, pointers only 4-byte aligned.  -22 for a null pointer with n > 0 or overlapping ranges. */
 int a3d_swap_f32(float* a, float* b, size_t n, void* stream);
