@@ -21,7 +21,7 @@ import torch
 from .diffusion import check_sampling_call, _graph_replay
 
 _TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight",
-            "scene_mask", "clear_margin", "clear_skip", "guide")
+            "scene_mask", "clear_margin", "clear_skip", "guide", "solver_order", "lower_order_final")
 
 
 def _same_tensors(a, b):
@@ -233,7 +233,7 @@ class Actioner:
         (B, history, >= action_dim), read only with predict_keypose=False; trajectory_mask (B, L), needed with
         predict_trajectory=True.  Returns {"action": (B, 8) or gt_action[:, -1], "trajectory": compute_trajectory's result or None,
         "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps, select,
-        rot_weight, scene_mask, clear_margin, clear_skip, guide) go to compute_trajectory unchanged (a rule that weighs "clearance"
+        rot_weight, scene_mask, clear_margin, clear_skip, guide, solver_order, lower_order_final) go to compute_trajectory unchanged (a rule that weighs "clearance"
         scores the candidates against pcds[:, -1], and `guide` steers the waypoints off that cloud while they are drawn); with select the candidates are ranked on the device, "trajectory" is the
         selected one (B, L, 8) and self.last_ranking mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
         and the sampling loop as graphs."""

@@ -893,6 +893,8 @@ __global__ __launch_bounds__(512) void dn_rest_loop_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ tail
+// HIST: the history term of a multistep schedule (a3d_ddpm_step_hist's rule: added last, only where kappa != 0; p.hist, p.kappa_*)
+template <bool HIST>
 __global__ __launch_bounds__(512) void dn_tail_kernel(const float* __restrict__ pos_feats, const float* __restrict__ rot_feats,
                                                       const float* __restrict__ traj, int D, a3d_dn_tail_params p,
                                                       float* __restrict__ traj_out, int L, int E, int row, int terminal, int warm) {
@@ -922,6 +924,11 @@ __global__ __launch_bounds__(512) void dn_tail_kernel(const float* __restrict__ 
       const float x0 = fminf(fmaxf(mo, -1.0f), 1.0f);
       out = cf[0] * x0 + cf[1] * traj[gi];
       if (p.noise) out += cf[2] * p.noise[gi];
+      if (HIST) {
+        const float kap = ((c < 3) ? p.kappa_pos : p.kappa_rot)[row];
+        if (kap != 0.f) out += kap * (x0 - p.hist[gi]);
+        p.hist[gi] = x0;
+      }
     }
     traj_out[gi] = out;
   }
@@ -1336,7 +1343,12 @@ __device__ __forceinline__ bool dnp_run_ops(float* smem, const DnOpTable& tab, i
 
 constexpr int DNP_LDS_FLOATS = DR * (4 * LDX + LDQK + LDH) + DN_PS + 2 * DR * LDX + 256 + 16 + 160;
 
-// ---- sample role
+// ---- sample role.  HIST: the tail adds the history term of a multistep schedule (tail.hist / kappa_*, a3d_ddpm_step_hist's rule);
+// the previous step's clipped prediction lives in one more [16][16] LDS tile BEHIND the DNP_LDS_FLOATS of the map below (the launch
+// asks for DNP_HIST_FLOATS more), loaded from tail.hist when the launch starts and stored back by every non-terminal step, so that
+// a chain cut into several launches continues.  An instance of its own: the one without it is the code of every other call.
+constexpr int DNP_HIST_FLOATS = 256;
+template <bool HIST>
 __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem) {
   const DnPersist& a = dnp_args(ap);
   float* smem0 = smem;
@@ -1380,6 +1392,14 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
   for (int i = t; i < 256; i += blockDim.x) {
     const int r = i >> 4, c = i & 15;
     Tr[i] = (r < L && c < D) ? a.traj[((size_t)bs * Lf + r0 + r) * D + c] : 0.f;
+  }
+  if (HIST && role == 0) {
+    const float* hg = dnp_args(ap).tail.hist;
+    float* Hh = smem + DNP_LDS_FLOATS;
+    for (int i = t; i < DNP_HIST_FLOATS; i += blockDim.x) {
+      const int r = i >> 4, c = i & 15;
+      Hh[i] = (r < L && c < D) ? hg[((size_t)bs * Lf + r0 + r) * D + c] : 0.f;
+    }
   }
   for (int i = t; i < 4 * DR * LDX; i += blockDim.x) smem[i] = 0.f;          // pads of the four row tiles
   __syncthreads();
@@ -1644,6 +1664,13 @@ __device__ __forceinline__ void dnp_sample_role(const DnPersist* ap, float* smem
           const float x0 = fminf(fmaxf(mo, -1.0f), 1.0f);
           out = cf[0] * x0 + cf[1] * old;
           if (p.noise) out += cf[2] * p.noise[(size_t)row * a.B * Lf * D + gi];
+          if (HIST) {
+            float* Hh = smem + DNP_LDS_FLOATS;
+            const float kap = ((c < 3) ? p.kappa_pos : p.kappa_rot)[row];
+            if (kap != 0.f) out += kap * (x0 - Hh[r * 16 + c]);
+            Hh[r * 16 + c] = x0;                         // this thread's own element at every step: no barrier
+            p.hist[gi] = x0;                             // read by the NEXT launch of a segmented chain
+          }
         }
         Tr[r * 16 + c] = out;
         dnp_st(&a.traj[gi], out);                    // the helper workgroup reads the rows next step
@@ -1676,9 +1703,10 @@ __global__ __launch_bounds__(256) void dn_persist_poison_kernel(float* __restric
   if (sync[2] == 0) return;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) traj[i] = __builtin_nanf("");
 }
+template <bool HIST>
 __global__ __launch_bounds__(512) void dn_persist_kernel(const DnPersist* __restrict__ ap, int U) {      // U: sample-role workgroups (2 per unit)
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  if ((int)blockIdx.x < U) dnp_sample_role(ap, smem);
+  if ((int)blockIdx.x < U) dnp_sample_role<HIST>(ap, smem);
   else dnp_stream_role(ap, smem);
 }
 
@@ -1785,6 +1813,23 @@ extern "C" int a3d_dn_rest(const float* x_in, const float* traj, int D, const fl
   return check_launch("a3d_dn_rest");
 }
 
+// The history term of a tail block (a3d_dn_tail_params.hist / kappa_pos / kappa_rot): 1 = all three given, 0 = none, -1 (error set)
+// = some but not all, or given to an entry whose tables are indexed by timestep (by_position false: kappa is indexed by step position)
+static int dn_tail_hist(const char* name, const a3d_dn_tail_params* p, bool by_position) {
+  const int n = (p->hist ? 1 : 0) + (p->kappa_pos ? 1 : 0) + (p->kappa_rot ? 1 : 0);
+  if (n == 0) return 0;
+  if (n != 3) {
+    set_error("%s: the history term needs hist, kappa_pos and kappa_rot together (got %s%s%s)", name, p->hist ? "hist " : "",
+              p->kappa_pos ? "kappa_pos " : "", p->kappa_rot ? "kappa_rot" : "");
+    return -1;
+  }
+  if (!by_position) {
+    set_error("%s: hist / kappa tables belong to a sampler schedule (tables by step position): use the _sched entry", name);
+    return -1;
+  }
+  return 1;
+}
+
 // ---- persistent sampler: host side
 static int dnp_nsub(int H) { return (H <= 8 && 8 % H == 0) ? 8 / H : 1; }
 
@@ -1862,6 +1907,8 @@ static int dnp_launch(const char* name, const a3d_dn_layer_params* layers_dev, i
               S, Sp, nsplit, n_traj, n_pos, n_rot, nsteps, row_label, row_first);
     return A3D_ERR_ARG;
   }
+  const int hist = dn_tail_hist(name, tail, row_inc == 1);           // row_inc 1: the schedule entries (tables by step position)
+  if (hist < 0) return A3D_ERR_ARG;
   if (head->lang_kv && (size_t)head->S_lang * 2 * E > (size_t)DR * (LDQK + LDH) + DN_PS) {
     set_error("%s: %d instruction tokens do not fit the LDS staging", name, head->S_lang);
     return A3D_ERR_ARG;
@@ -1898,10 +1945,15 @@ static int dnp_launch(const char* name, const a3d_dn_layer_params* layers_dev, i
   if (rc) return rc;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)dn_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute((const void*)dn_persist_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    (void)hipFuncSetAttribute((const void*)dn_persist_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     attr_set = true;
   }
-  hipLaunchKernelGGL(dn_persist_kernel, dim3(2 * U + nworkers), dim3(512), (size_t)DNP_LDS_FLOATS * sizeof(float), s, a_dev, 2 * U);
+  if (hist)
+    hipLaunchKernelGGL(dn_persist_kernel<true>, dim3(2 * U + nworkers), dim3(512), (size_t)(DNP_LDS_FLOATS + DNP_HIST_FLOATS) * sizeof(float),
+                       s, a_dev, 2 * U);
+  else
+    hipLaunchKernelGGL(dn_persist_kernel<false>, dim3(2 * U + nworkers), dim3(512), (size_t)DNP_LDS_FLOATS * sizeof(float), s, a_dev, 2 * U);
   rc = check_launch("a3d_dn_persist");
   if (rc) return rc;
   hipLaunchKernelGGL(dn_persist_poison_kernel, dim3(std::min(cdiv(B * L * D, 256), 64)), dim3(256), 0, s, traj, B * L * D, sync);
@@ -1936,25 +1988,32 @@ extern "C" int a3d_dn_persist_group(const a3d_dn_layer_params* layers_dev, int n
 }
 
 static int dn_tail_launch(const char* name, const float* pos_feats, const float* rot_feats, const float* traj, int D,
-                          const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int row, int terminal, void* stream) {
+                          const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int row, int terminal, bool by_position,
+                          void* stream) {
   if (!pos_feats || !rot_feats || !traj || !p || !traj_out || B <= 0 || L <= 0 || L > DR || E <= 0 || E > 128 || D < 4 || D > 16 ||
       row < 0 || (terminal != 0 && terminal != 1) || !p->pos_w0 || !p->rot_w0 || !p->coef_pos || !p->coef_rot || (p->cond_mask && !p->cond_data)) {
     set_error("%s: bad argument", name);
     return A3D_ERR_ARG;
   }
-  hipLaunchKernelGGL(dn_tail_kernel, dim3(B), dim3(dn_threads()), 0, (hipStream_t)stream, pos_feats, rot_feats, traj, D, *p, traj_out, L,
-                     E, row, terminal, dn_warm());
+  const int hist = dn_tail_hist(name, p, by_position);
+  if (hist < 0) return A3D_ERR_ARG;
+  if (hist)
+    hipLaunchKernelGGL(dn_tail_kernel<true>, dim3(B), dim3(dn_threads()), 0, (hipStream_t)stream, pos_feats, rot_feats, traj, D, *p,
+                       traj_out, L, E, row, terminal, dn_warm());
+  else
+    hipLaunchKernelGGL(dn_tail_kernel<false>, dim3(B), dim3(dn_threads()), 0, (hipStream_t)stream, pos_feats, rot_feats, traj, D, *p,
+                       traj_out, L, E, row, terminal, dn_warm());
   return check_launch(name);
 }
 
 extern "C" int a3d_dn_tail(const float* pos_feats, const float* rot_feats, const float* traj, int D,
                            const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int t_step, void* stream) {
-  return dn_tail_launch("a3d_dn_tail", pos_feats, rot_feats, traj, D, p, traj_out, B, L, E, t_step, t_step == 0, stream);
+  return dn_tail_launch("a3d_dn_tail", pos_feats, rot_feats, traj, D, p, traj_out, B, L, E, t_step, t_step == 0, false, stream);
 }
 
 extern "C" int a3d_dn_tail_sched(const float* pos_feats, const float* rot_feats, const float* traj, int D,
                                  const a3d_dn_tail_params* p, float* traj_out, int B, int L, int E, int row, int terminal, void* stream) {
-  return dn_tail_launch("a3d_dn_tail_sched", pos_feats, rot_feats, traj, D, p, traj_out, B, L, E, row, terminal, stream);
+  return dn_tail_launch("a3d_dn_tail_sched", pos_feats, rot_feats, traj, D, p, traj_out, B, L, E, row, terminal, true, stream);
 }
 
 extern "C" int a3d_rope_rows_f32(const float* Y, int ldy, const float* xyz, const float* freq, float scale, float* out, int B,

@@ -31,12 +31,16 @@ __global__ void ddpm_add_noise_kernel(const float* __restrict__ x0, const float*
   }
 }
 
-// coef tables: [rows][3] = (coef_x0, coef_xt, sigma) per schedule; terminal: the in-painted network output is the result
+// coef tables: [rows][3] = (coef_x0, coef_xt, sigma) per schedule; terminal: the in-painted network output is the result.
+// HIST (a3d_ddpm_step_hist): the history term of a multistep schedule, kappa[row] (x0 - hist), added LAST and only where kappa != 0
+// (so that a table of zeros gives the bits of the instance without it); every non-terminal step leaves its x0 in hist.
+template <bool HIST>
 __global__ void ddpm_step_kernel(const float* __restrict__ model_out, const float* __restrict__ sample,
                                  const float* __restrict__ noise, const float* __restrict__ cond_data,
                                  const unsigned char* __restrict__ cond_mask, const float* __restrict__ coef_pos,
                                  const float* __restrict__ coef_rot, float* __restrict__ out, int rows, int D,
-                                 int npos, int row, int terminal) {
+                                 int npos, int row, int terminal, float* __restrict__ hist,
+                                 const float* __restrict__ kappa_pos, const float* __restrict__ kappa_rot) {
   const size_t total = (size_t)rows * D;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % D);
@@ -47,6 +51,11 @@ __global__ void ddpm_step_kernel(const float* __restrict__ model_out, const floa
     const float x0 = fminf(fmaxf(mo, -1.0f), 1.0f);
     float prev = cf[0] * x0 + cf[1] * sample[i];
     if (noise) prev += cf[2] * noise[i];
+    if (HIST) {
+      const float kap = ((c < npos) ? kappa_pos : kappa_rot)[row];
+      if (kap != 0.f) prev += kap * (x0 - hist[i]);
+      hist[i] = x0;
+    }
     out[i] = prev;
   }
 }
@@ -354,7 +363,7 @@ extern "C" int a3d_ddpm_step(const float* model_out, const float* sample, const 
                              const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out,
                              int rows, int D, int npos, int t, void* stream) {
   if (!model_out || !sample || !coef_pos || !coef_rot || !out || rows <= 0 || D <= 0 || t < 0 || (cond_mask && !cond_data)) { set_error("a3d_ddpm_step: bad argument"); return A3D_ERR_ARG; }
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, t, t == 0);
+  hipLaunchKernelGGL(ddpm_step_kernel<false>, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, t, t == 0, nullptr, nullptr, nullptr);
   return check_launch("a3d_ddpm_step");
 }
 extern "C" int a3d_ddpm_step_sched(const float* model_out, const float* sample, const float* noise, const float* cond_data,
@@ -362,8 +371,22 @@ extern "C" int a3d_ddpm_step_sched(const float* model_out, const float* sample, 
                                    int rows, int D, int npos, int row, int terminal, void* stream) {
   if (!model_out || !sample || !coef_pos || !coef_rot || !out || rows <= 0 || D <= 0 || row < 0 || (terminal != 0 && terminal != 1) ||
       (cond_mask && !cond_data)) { set_error("a3d_ddpm_step_sched: bad argument"); return A3D_ERR_ARG; }
-  hipLaunchKernelGGL(ddpm_step_kernel, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, row, terminal);
+  hipLaunchKernelGGL(ddpm_step_kernel<false>, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, row, terminal, nullptr, nullptr, nullptr);
   return check_launch("a3d_ddpm_step_sched");
+}
+extern "C" int a3d_ddpm_step_hist(const float* model_out, const float* sample, const float* noise, const float* cond_data,
+                                  const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out,
+                                  int rows, int D, int npos, int row, int terminal, float* hist, const float* kappa_pos,
+                                  const float* kappa_rot, void* stream) {
+  if (!model_out || !sample || !coef_pos || !coef_rot || !out || rows <= 0 || D <= 0 || row < 0 || (terminal != 0 && terminal != 1) ||
+      (cond_mask && !cond_data)) { set_error("a3d_ddpm_step_hist: bad argument"); return A3D_ERR_ARG; }
+  if (!hist || !kappa_pos || !kappa_rot) {
+    set_error("a3d_ddpm_step_hist: the history term needs hist, kappa_pos and kappa_rot (got %s%s%s)", hist ? "hist " : "",
+              kappa_pos ? "kappa_pos " : "", kappa_rot ? "kappa_rot" : "");
+    return A3D_ERR_ARG;
+  }
+  hipLaunchKernelGGL(ddpm_step_kernel<true>, dim3(gsz((size_t)rows * D)), dim3(256), 0, (hipStream_t)stream, model_out, sample, noise, cond_data, cond_mask, coef_pos, coef_rot, out, rows, D, npos, row, terminal, hist, kappa_pos, kappa_rot);
+  return check_launch("a3d_ddpm_step_hist");
 }
 extern "C" int a3d_adaln_fwd(const float* x, const float* mod, float* y, int B, int L, int E, void* stream) {
   if (!x || !mod || !y || B <= 0 || L <= 0 || E <= 0) { set_error("a3d_adaln_fwd: bad argument"); return A3D_ERR_ARG; }

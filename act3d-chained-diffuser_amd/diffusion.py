@@ -15,7 +15,7 @@ What is restructured, with identical results:
 The DDPM schedules restate diffusers' DDPMScheduler (third-party, un-pinned -> parity unpinned).
 Additive keyword arguments: `noise`, `timesteps` (training) and `init_noise`, `step_noise` (sampling) inject the random
 draws; `visual_tokens` bypasses the backbone + FPN; `num_inference_steps` / `scheduler` / `eta` select a few-step sampler
-schedule; `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8);
+schedule (`scheduler="dpm++"` with `solver_order` / `lower_order_final`: the DPM-Solver++ 2M multistep solver); `num_samples=G` samples G candidate trajectories per scene from one shared context K/V cache -> (B, G, L, 8);
 `fused_conditioning=True` builds the sampler's conditioning tensors in one launch (a3d_traj_condition); `select` / `rot_weight`
 rank the candidates on the device and return the selected trajectory (rank_trajectories, a3d_traj_rank), optionally against the
 observed point cloud (trajectory_clearance, a3d_traj_clearance: the "clearance" term of a select rule); `guide` steers the waypoints
@@ -63,11 +63,12 @@ class DDPMTables:
 
 
 # ------------------------------------------------------------------------------------------------ sampler schedules
-SCHEDULERS = ("ddpm", "ddim")
+SCHEDULERS = ("ddpm", "ddim", "dpm++")
 
 
-def check_sampler_args(T, num_inference_steps=None, scheduler="ddpm", eta=0.0):
-    """Validates the sampler-schedule arguments of compute_trajectory on the host; returns K (None -> T)."""
+def check_sampler_args(T, num_inference_steps=None, scheduler="ddpm", eta=0.0, solver_order=2, lower_order_final=True):
+    """Validates the sampler-schedule arguments of compute_trajectory on the host; returns K (None -> T).  solver_order (1 or 2) and
+    lower_order_final (a bool) belong to scheduler "dpm++": any other scheduler takes only their defaults; "dpm++" takes eta = 0."""
     if scheduler not in SCHEDULERS:
         raise ValueError("unknown scheduler %r (one of %s)" % (scheduler, ", ".join(SCHEDULERS)))
     K = T if num_inference_steps is None else num_inference_steps
@@ -77,7 +78,22 @@ def check_sampler_args(T, num_inference_steps=None, scheduler="ddpm", eta=0.0):
         raise ValueError("eta must lie in [0, 1], got %r" % (eta,))
     if scheduler == "ddpm" and float(eta) != 0.0:
         raise ValueError("eta = %r needs scheduler='ddim' (the ancestral DDPM sampler has no eta)" % (eta,))
+    check_solver_args(scheduler, eta, solver_order, lower_order_final)
     return K
+
+
+def check_solver_args(scheduler, eta, solver_order, lower_order_final):
+    """The part of check_sampler_args that needs no chain length: what "dpm++" takes and what only "dpm++" takes."""
+    if isinstance(solver_order, bool) or solver_order not in (1, 2):
+        raise ValueError("solver_order must be 1 or 2, got %r" % (solver_order,))
+    if not isinstance(lower_order_final, bool):
+        raise ValueError("lower_order_final must be True or False, got %r" % (lower_order_final,))
+    if scheduler == "dpm++":
+        if float(eta) != 0.0:
+            raise ValueError("eta = %r: scheduler='dpm++' is deterministic (eta must be 0)" % (eta,))
+    elif solver_order != 2 or lower_order_final is not True:
+        raise ValueError("solver_order / lower_order_final belong to scheduler='dpm++', got solver_order=%r, lower_order_final=%r "
+                         "with scheduler=%r" % (solver_order, lower_order_final, scheduler))
 
 
 def check_num_samples(num_samples):
@@ -108,7 +124,8 @@ def sampler_coefficients(acp, timesteps, stride, scheduler="ddpm", eta=0.0):
     arithmetic (with every timestep and stride 1 these are DDPMTables.coef_*, bit for bit).
     "ddim": Song et al. 2021 eq. 12 with eps DERIVED FROM THE CLIPPED x0, eps = (x_t - sqrt(a_t) clip(x0)) / sqrt(1 - a_t) -- the
     choice that keeps the update a three-coefficient form:  sigma = eta sqrt((1 - a_prev) / (1 - a_t)) sqrt(1 - a_t / a_prev),
-    c1 = sqrt(1 - a_prev - sigma^2) / sqrt(1 - a_t),  c0 = sqrt(a_prev) - c1 sqrt(a_t),  c2 = sigma; evaluated in float64."""
+    c1 = sqrt(1 - a_prev - sigma^2) / sqrt(1 - a_t),  c0 = sqrt(a_prev) - c1 sqrt(a_t),  c2 = sigma; evaluated in float64.
+    "dpm++": the "ddim" rows at eta = 0 by the same code (the first-order part of DPM-Solver++; the rest is sampler_kappa)."""
     rows = []
     for t in timesteps:
         prev = t - stride
@@ -129,23 +146,61 @@ def sampler_coefficients(acp, timesteps, stride, scheduler="ddpm", eta=0.0):
     return torch.stack(rows)
 
 
+def _log_snr_half(a):
+    """lambda(a) = 1/2 ln(a / (1 - a)) = ln(alpha / sigma) of a cumulative alpha product a (a Python float, evaluated in float64)"""
+    return 0.5 * math.log(a / (1.0 - a))
+
+
+def sampler_kappa(acp, timesteps, stride, solver_order=2, lower_order_final=True):
+    """[K] float64 coefficients of the history term of DPM-Solver++ (2M) (Lu et al. 2022, Algorithm 2) in its data-prediction form.
+    With D_i = clip(in-painted network output at step position i), lambda(a) = 1/2 ln(a / (1 - a)), the step at position i from
+    t = timesteps[i] to prev = t - stride and h_i = lambda(a_prev) - lambda(a_t), the multistep update
+        x_prev = (sigma_prev / sigma_t) x_t - alpha_prev (e^{-h_i} - 1) [(1 + 1 / (2 rho)) D_i - 1 / (2 rho) D_{i-1}],  rho = h_{i-1} / h_i
+    is the "ddim", eta = 0 row of sampler_coefficients plus one term on the previous prediction:
+        x_prev = c0 D_i + c1 x_t + kappa_i (D_i - D_{i-1}),    kappa_i = sqrt(a_prev) (1 - e^{-h_i}) h_i / (2 h_{i-1}).
+    kappa_i = 0 (a first-order step) at position 0 (no history yet), everywhere for solver_order 1, at the terminal position (prev < 0:
+    the step returns the network output) and, with lower_order_final, at the last update, position K - 2: it lands on timestep 0,
+    where h is several times the steps before it and the extrapolation overshoots (kappa up to 1.6; diffusers' lower_order_final)."""
+    K = len(timesteps)
+    lam = lambda t: _log_snr_half(float(acp[t].double()))
+    out = torch.zeros(K, dtype=torch.float64)
+    if solver_order == 1:
+        return out
+    for i in range(1, K):
+        t, prev = timesteps[i], timesteps[i] - stride
+        if prev < 0 or (lower_order_final and i == K - 2):
+            continue
+        h, h_last = lam(prev) - lam(t), lam(t) - lam(timesteps[i - 1])
+        out[i] = math.sqrt(float(acp[prev].double())) * (1.0 - math.exp(-h)) * h / (2.0 * h_last)
+    return out
+
+
 class SamplerSchedule:
     """A K-step sampler over the T training timesteps of a DDPMTables (its position and rotation schedules): the timestep list and
     the per-step coefficient tables coef_pos / coef_rot [K][3], indexed by step POSITION i (the i-th executed step), see
     sampler_timesteps / sampler_coefficients.  The step at timestep 0 (position K - 1) is terminal for both schedulers: it returns
-    the in-painted network output and adds no noise, as the full chain does.  noise_free: no step reads a noise draw (DDIM, eta = 0)."""
+    the in-painted network output and adds no noise, as the full chain does.  noise_free: no step reads a noise draw (DDIM, eta = 0,
+    and "dpm++").  "dpm++" (DPM-Solver++ 2M): coef_* are the "ddim", eta = 0 rows, bit for bit, and kappa_pos / kappa_rot [K] weigh
+    the history term (sampler_kappa); they are None for the other schedulers, whose key is unchanged."""
 
-    def __init__(self, tables, num_inference_steps=None, scheduler="ddpm", eta=0.0):
+    def __init__(self, tables, num_inference_steps=None, scheduler="ddpm", eta=0.0, solver_order=2, lower_order_final=True):
         self.T = tables.T
-        self.K = check_sampler_args(tables.T, num_inference_steps, scheduler, eta)
+        self.K = check_sampler_args(tables.T, num_inference_steps, scheduler, eta, solver_order, lower_order_final)
         self.scheduler, self.eta = scheduler, float(eta)
+        self.solver_order, self.lower_order_final = solver_order, lower_order_final
         self.timesteps, self.stride = sampler_timesteps(self.T, self.K)
         dev = tables.acp_pos.device
         self.coef_pos, self.coef_rot = (
             sampler_coefficients(acp.cpu(), self.timesteps, self.stride, scheduler, eta).float().contiguous().to(dev)
             for acp in (tables.acp_pos, tables.acp_rot))
-        self.noise_free = scheduler == "ddim" and self.eta == 0.0
+        self.noise_free = scheduler in ("ddim", "dpm++") and self.eta == 0.0
         self.key = (self.K, scheduler, self.eta)
+        self.kappa_pos = self.kappa_rot = None
+        if scheduler == "dpm++":
+            self.kappa_pos, self.kappa_rot = (
+                sampler_kappa(acp.cpu(), self.timesteps, self.stride, solver_order, lower_order_final).float().contiguous().to(dev)
+                for acp in (tables.acp_pos, tables.acp_rot))
+            self.key = self.key + (solver_order, lower_order_final)
 
 
 # ------------------------------------------------------------------------------------------------ pose <-> signal
@@ -896,15 +951,20 @@ class DiffusionHead(nn.Module):
             hp.ln_g, hp.ln_b = ll.norm_12.weight.data_ptr(), ll.norm_12.bias.data_ptr()
         return hp
 
-    def _dn_tail_params(self, noise, cond_data, cond_mask_u8, tables):
-        """noise: what the launch reads -- the whole table (persistent sampler), one step's row (per-phase tail) or None."""
+    def _dn_tail_params(self, noise, cond_data, cond_mask_u8, tables, hist=None):
+        """noise: what the launch reads -- the whole table (persistent sampler), one step's row (per-phase tail) or None.
+        hist: the history buffer of a multistep schedule (tables.kappa_*), else None: the three fields stay NULL."""
         pr, rr = self.pos_regressor[0], self.rot_regressor[0]
-        return O.L.DnTailParams(pos_w0=pr[0].weight.data_ptr(), pos_b0=pr[0].bias.data_ptr(), pos_w1=pr[3].weight.data_ptr(),
-                                pos_b1=pr[3].bias.data_ptr(), rot_w0=rr[0].weight.data_ptr(), rot_b0=rr[0].bias.data_ptr(),
-                                rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(),
-                                noise=None if noise is None else noise.data_ptr(), cond_data=cond_data.data_ptr(),
-                                cond_mask=cond_mask_u8.data_ptr(), coef_pos=tables.coef_pos.data_ptr(),
-                                coef_rot=tables.coef_rot.data_ptr())
+        tp = O.L.DnTailParams(pos_w0=pr[0].weight.data_ptr(), pos_b0=pr[0].bias.data_ptr(), pos_w1=pr[3].weight.data_ptr(),
+                              pos_b1=pr[3].bias.data_ptr(), rot_w0=rr[0].weight.data_ptr(), rot_b0=rr[0].bias.data_ptr(),
+                              rot_w1=rr[3].weight.data_ptr(), rot_b1=rr[3].bias.data_ptr(),
+                              noise=None if noise is None else noise.data_ptr(), cond_data=cond_data.data_ptr(),
+                              cond_mask=cond_mask_u8.data_ptr(), coef_pos=tables.coef_pos.data_ptr(),
+                              coef_rot=tables.coef_rot.data_ptr())
+        if hist is not None:
+            assert tuple(hist.shape) == tuple(cond_data.shape) and hist.is_contiguous() and hist.dtype == torch.float32
+            tp.hist, tp.kappa_pos, tp.kappa_rot = hist.data_ptr(), tables.kappa_pos.data_ptr(), tables.kappa_rot.data_ptr()
+        return tp
 
     @staticmethod
     def _dn_mod(rec, k, row):
@@ -971,13 +1031,14 @@ class DiffusionHead(nn.Module):
         returns the trajectory after the last of them (a new tensor).  tables is what st was built on:
         a DDPMTables -- the timesteps first, first - 1, ... of the full chain (a3d_dn_persist), step_noise the (T, B, L, D) table;
         a SamplerSchedule -- the steps at POSITIONS first, first + 1, ... of the schedule (a3d_dn_persist_sched), step_noise
-        (K, B, L, D) by position, or None for a noise-free schedule.
+        (K, B, L, D) by position, or None for a noise-free schedule.  st["hist"] (a "dpm++" schedule): the history buffer (B, L, D) the
+        launch starts from and leaves its last prediction in.
         A state marked for candidate groups (ps["group"]: compute_trajectory(num_samples=G), always on a schedule) goes through
         a3d_dn_persist_group: traj holds scenes x n_cand trajectories, scene-major, against the per-scene cache of st."""
         Lb = O.L
         ps = st["persist"]
         B, Ln, D = traj.shape
-        hp, tp = self._dn_head_params(st), self._dn_tail_params(step_noise, cond_data, cond_mask_u8, tables)
+        hp, tp = self._dn_head_params(st), self._dn_tail_params(step_noise, cond_data, cond_mask_u8, tables, st.get("hist"))
         out = traj.clone()
         self._last_persist = ps                      # tests read the abort word (sync[2]) after synchronising
         nt, npos, nrot = ps["stacks"]
@@ -1049,7 +1110,7 @@ class DiffusionHead(nn.Module):
             pf = run_layer(pf, rec, st["ws"])
         cur.wait_stream(side)
         rf.record_stream(cur)
-        tp = self._dn_tail_params(noise, cond_data, cond_mask_u8, tables)
+        tp = self._dn_tail_params(noise, cond_data, cond_mask_u8, tables, st.get("hist"))
         tail = (pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, O.C_byref(tp), out.data_ptr(), B, Ln, E, int(row))
         if not isinstance(tables, SamplerSchedule):
             Lb.call("a3d_dn_tail", *tail, Lb.stream())
@@ -1150,7 +1211,7 @@ _SamplingCall = collections.namedtuple("_SamplingCall", ("G", "K", "guide", "w_c
 
 def check_sampling_call(B, Ln, D, T, pcd_obs, have_goal=True, *, num_samples=None, num_inference_steps=None, scheduler="ddpm", eta=0.0,
                         init_noise=None, step_noise=None, n_steps=None, select=None, rot_weight=1.0, scene_mask=None,
-                        clear_margin=0.05, clear_skip=(1, 1), guide=None):
+                        clear_margin=0.05, clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True):
     """Every host-side check of a sampling call (compute_trajectory, Actioner.predict), on shapes and Python values alone: nothing
     is launched, so a bad argument raises before any kernel runs.  B scenes of Ln steps and D = pose width + 2 signal channels; T:
     the chain length, or None where the caller leaves the schedule and the noise tables to the sampler (Actioner.predict, whose
@@ -1170,11 +1231,14 @@ def check_sampling_call(B, Ln, D, T, pcd_obs, have_goal=True, *, num_samples=Non
         if w_clear != 0.0:
             scene = check_scene(pcd_obs, scene_mask, B) + check_clearance_args(clear_margin, clear_skip)
     K = None
-    if T is not None and (num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0):
-        K = check_sampler_args(T, num_inference_steps, scheduler, eta)
+    if T is not None and (num_inference_steps is not None or scheduler != "ddpm" or eta != 0.0 or solver_order != 2
+                          or lower_order_final is not True):
+        K = check_sampler_args(T, num_inference_steps, scheduler, eta, solver_order, lower_order_final)
         if step_noise is not None and step_noise.shape[0] != K:
             raise ValueError("step_noise has %d leading rows for a schedule of %d steps (one row per step position)"
                              % (step_noise.shape[0], K))
+    if T is None:
+        check_solver_args(scheduler, eta, solver_order, lower_order_final)
     guide = check_guide(guide)
     if guide is not None:
         check_guide_shape(G or 1, Ln, D)
@@ -1257,11 +1321,12 @@ class DiffusionPlanner(nn.Module):
             self._schedules = {}
         return self._tables
 
-    def schedule(self, device, num_inference_steps=None, scheduler="ddpm", eta=0.0):
-        """The SamplerSchedule of (K, scheduler, eta) on `device` (built once and kept: a captured graph addresses its tables),
-        with time_sin = the sinusoidal embedding rows of its K timesteps in step order."""
+    def schedule(self, device, num_inference_steps=None, scheduler="ddpm", eta=0.0, solver_order=2, lower_order_final=True):
+        """The SamplerSchedule of (K, scheduler, eta[, solver_order, lower_order_final]) on `device` (built once and kept: a captured
+        graph addresses its tables), with time_sin = the sinusoidal embedding rows of its K timesteps in step order."""
         tb = self.tables(device)
-        key = (check_sampler_args(self.n_steps, num_inference_steps, scheduler, eta), scheduler, float(eta))
+        key = (check_sampler_args(self.n_steps, num_inference_steps, scheduler, eta, solver_order, lower_order_final), scheduler,
+               float(eta), solver_order, lower_order_final)
         if key not in self._schedules:
             sc = SamplerSchedule(tb, *key)
             sc.time_sin = self._time_tables["sin"][torch.tensor(sc.timesteps, device=device)].contiguous()
@@ -1338,12 +1403,17 @@ class DiffusionPlanner(nn.Module):
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
                            return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None,
                            fused_conditioning=False, select=None, rot_weight=1.0, scene_mask=None, clear_margin=0.05,
-                           clear_skip=(1, 1), guide=None):
+                           clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
         i used by the i-th executed step, and is neither drawn nor read for "ddim" with eta = 0.  n_steps truncates the (scheduled)
         step list for fixtures; a truncated run has no terminal step.
+        scheduler = "dpm++": DPM-Solver++ (2M), the second-order multistep solver for a 5 - 20 step budget (sampler_kappa): the
+        "ddim", eta = 0 update plus one term on the previous step's prediction -- no further network evaluation, noise table or launch.
+        solver_order = 1 is "ddim" with eta = 0, bit for bit; lower_order_final = True (default) makes the last update, the one that
+        lands on timestep 0, first-order.  eta must be 0, no step noise is drawn or read (a given step_noise is ignored), and the two
+        keywords are accepted only with this scheduler.
         num_samples = G (an integer >= 1) draws G candidate trajectories per scene and returns (B, G, L, 8) (trace entries
         (B, G, L, D)): init_noise is then (B, G, L, D) and step_noise (steps, B, G, L, D); every other input stays per scene.  The
         step-invariant setup (encoding, K / V cache, instruction rows) runs once per scene and the persistent sampler streams a
@@ -1379,14 +1449,15 @@ class DiffusionPlanner(nn.Module):
         call = check_sampling_call(B_scene, Ln, D, self.n_steps, pcd_obs, goal_gripper is not None, num_samples=num_samples,
                                    num_inference_steps=num_inference_steps, scheduler=scheduler, eta=eta, init_noise=init_noise,
                                    step_noise=step_noise, n_steps=n_steps, select=select, rot_weight=rot_weight, scene_mask=scene_mask,
-                                   clear_margin=clear_margin, clear_skip=clear_skip, guide=guide)
+                                   clear_margin=clear_margin, clear_skip=clear_skip, guide=guide, solver_order=solver_order,
+                                   lower_order_final=lower_order_final)
         # ---- the plan: which launches serve the call, from the shapes and the CU count alone
         multi = head.attn_rounds * head.feat_scales > 1
         plan = sampler_plan(B_scene, call.G, Ln, D, head.curr_gripper_embed.weight.shape[1], head.num_attn_heads, self.n_steps,
                             torch.cuda.get_device_properties(dev).multi_processor_count, multi, fused, num_inference_steps, scheduler,
                             eta, n_steps)
         tb = self.tables(dev)
-        sched = self.schedule(dev, plan.K, scheduler, eta) if plan.scheduled else None
+        sched = self.schedule(dev, plan.K, scheduler, eta, solver_order, lower_order_final) if plan.scheduled else None
         c = self._condition(plan, sched, call.G, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper,
                             init_noise, step_noise, visual_tokens, fused_conditioning)
         replay = use_graph and not return_trace
@@ -1487,7 +1558,7 @@ class DiffusionPlanner(nn.Module):
                 static = list(state["tensors"])
         static = static + ([] if c.step_noise is None else [c.step_noise]) + [c.cond_data, c.cond_mask_u8, c.kmask]
         if sched is not None:
-            static = static + [sched.coef_pos, sched.coef_rot]
+            static = static + [sched.coef_pos, sched.coef_rot] + ([] if sched.kappa_pos is None else [sched.kappa_pos, sched.kappa_rot])
         gd = None
         if call.guide is not None:
             # what the guide pair reads: the caller's cloud and masks in place; a captured graph addresses copies the planner owns,
@@ -1516,6 +1587,13 @@ class DiffusionPlanner(nn.Module):
             # (a ctypes table, a pageable host-to-device copy = a host sync, five allocations) that would be thrown away
             state["persist"] = self._graph["state"]["persist"] if captured else \
                 head._build_persist(state, c.B, Ln, time_sin.shape[0], plan.group)
+        if sched is not None and sched.kappa_pos is not None:
+            # the history buffer of a multistep schedule: every non-terminal step leaves its clipped prediction there for the next one,
+            # whichever launch runs it.  It belongs to the sampler state and, like the persistent sampler's buffers, to the captured
+            # graph: a replay addresses the buffer of the capturing call (static holds it so that it stays with the graph; nothing
+            # is copied into it -- position 0 never reads it)
+            state["hist"] = self._graph["state"]["hist"] if captured else torch.zeros_like(c.cond_data)
+            static = static + [state["hist"]]
         if plan.group and state.get("persist") is None:
             raise RuntimeError("num_samples: the per-scene cache was built for a3d_dn_persist_group, which cannot serve this call")
         return state, static, key, gd
@@ -1568,8 +1646,11 @@ class DiffusionPlanner(nn.Module):
                         out = head.denoise_tokens_cached(x, c.kmask, t, state, self._time_tables)
                     if term is None:
                         x = O.ddpm_step(out, x, nz, c.cond_data, c.cond_mask_u8, tables.coef_pos, tables.coef_rot, row)
-                    else:
+                    elif state.get("hist") is None:
                         x = O.ddpm_step_sched(out, x, nz, c.cond_data, c.cond_mask_u8, tables.coef_pos, tables.coef_rot, row, term)
+                    else:
+                        x = O.ddpm_step_sched(out, x, nz, c.cond_data, c.cond_mask_u8, tables.coef_pos, tables.coef_rot, row, term,
+                                              hist=state["hist"], kappa_pos=tables.kappa_pos, kappa_rot=tables.kappa_rot)
                 if guided:
                     self._guide_step(x, i == n_exec - 1, call, c, gd)
                 if trace is not None:

@@ -35,7 +35,7 @@ DnRestParams = _struct("DnRestParams", [(n, _p) for n in (
 DnLayerParams = _struct("DnLayerParams", [("cross", DnCrossParams), ("rest", DnRestParams)])
 DnTailParams = _struct("DnTailParams", [(n, _p) for n in (
     "pos_w0", "pos_b0", "pos_w1", "pos_b1", "rot_w0", "rot_b0", "rot_w1", "rot_b1", "noise", "cond_data", "cond_mask", "coef_pos",
-    "coef_rot")])
+    "coef_rot", "hist", "kappa_pos", "kappa_rot")])
 
 # parameter / gradient blocks of the fused query-stream layer (a3d_qs_params / a3d_qs_grads)
 QsParams = _struct("QsParams", [(n, _p) for n in ("wv", "bv", "wo", "bo", "g1", "b1", "w1", "c1", "w2", "c2", "g2", "b2")])
@@ -198,6 +198,7 @@ SIGNATURES = {
     "a3d_ddpm_add_noise": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "a3d_ddpm_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "a3d_ddpm_step_sched": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "a3d_ddpm_step_hist": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "a3d_adaln_fwd": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "a3d_adaln_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "a3d_sinusoidal_emb": (_i, [_p, _p, _i, _i, _p]),

@@ -1808,13 +1808,20 @@ def ddpm_step(model_out, sample, noise, cond_data, cond_mask_u8, coef_pos, coef_
     return out
 
 
-def ddpm_step_sched(model_out, sample, noise, cond_data, cond_mask_u8, coef_pos, coef_rot, row, terminal, out=None):
+def ddpm_step_sched(model_out, sample, noise, cond_data, cond_mask_u8, coef_pos, coef_rot, row, terminal, out=None, hist=None,
+                    kappa_pos=None, kappa_rot=None):
     """ddpm_step on [K][3] tables indexed by step position (diffusion.SamplerSchedule): row = the step's position, terminal = the
-    step returns the in-painted network output."""
+    step returns the in-painted network output.  hist / kappa_pos / kappa_rot (all three): the history term of a multistep
+    schedule (a3d_ddpm_step_hist) -- hist, the shape of sample, is read where kappa[row] != 0 and updated in place."""
     out = torch.empty_like(sample) if out is None else out
-    L.call("a3d_ddpm_step_sched", model_out.data_ptr(), sample.data_ptr(), None if noise is None else noise.data_ptr(),
-           cond_data.data_ptr(), cond_mask_u8.data_ptr(), coef_pos.data_ptr(), coef_rot.data_ptr(), out.data_ptr(),
-           sample.numel() // sample.shape[-1], sample.shape[-1], 3, int(row), int(bool(terminal)), L.stream())
+    args = (model_out.data_ptr(), sample.data_ptr(), None if noise is None else noise.data_ptr(),
+            cond_data.data_ptr(), cond_mask_u8.data_ptr(), coef_pos.data_ptr(), coef_rot.data_ptr(), out.data_ptr(),
+            sample.numel() // sample.shape[-1], sample.shape[-1], 3, int(row), int(bool(terminal)))
+    if hist is None and kappa_pos is None and kappa_rot is None:
+        L.call("a3d_ddpm_step_sched", *args, L.stream())
+    else:
+        assert hist is None or (hist.shape == sample.shape and hist.is_contiguous() and hist.dtype == torch.float32)
+        L.call("a3d_ddpm_step_hist", *args, *(None if x is None else x.data_ptr() for x in (hist, kappa_pos, kappa_rot)), L.stream())
     return out
 
 

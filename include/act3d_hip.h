@@ -480,6 +480,14 @@ int a3d_ddpm_step(const float* model_out, const float* sample, const float* nois
 int a3d_ddpm_step_sched(const float* model_out, const float* sample, const float* noise, const float* cond_data,
                         const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out, int rows,
                         int D, int npos, int row, int terminal, void* stream);
+/* a3d_ddpm_step_sched with the history term of a second-order multistep schedule (DPM-Solver++ 2M in its data-prediction form):
+ * with x0 = clip(in-painted model_out, -1, 1) and k = kappa_pos[row] (channels < npos) or kappa_rot[row],
+ *   out = c0[row]*x0 + c1[row]*sample [+ c2[row]*noise];  if (k != 0) out += k * (x0 - hist);
+ * hist ([rows][D]) is read only where k != 0 and every non-terminal step stores its x0 there.  kappa_*: [K] by step position. */
+int a3d_ddpm_step_hist(const float* model_out, const float* sample, const float* noise, const float* cond_data,
+                       const unsigned char* cond_mask, const float* coef_pos, const float* coef_rot, float* out, int rows,
+                       int D, int npos, int row, int terminal, float* hist, const float* kappa_pos, const float* kappa_rot,
+                       void* stream);
 /* AdaLN: y = x * (1 + mod[:, :E]) + mod[:, E:]  (layers.py:273-290); mod: [B][2E], x: [B][L][E]. */
 int a3d_adaln_fwd(const float* x, const float* mod, float* y, int B, int L, int E, void* stream);
 int a3d_adaln_bwd(const float* x, const float* mod, const float* dy, float* dx, float* dmod, int B, int L, int E,
@@ -628,6 +636,11 @@ typedef struct {
   const float *noise, *cond_data;            /* [B][L][D]; noise NULL at t = 0 */
   const unsigned char* cond_mask;            /* [B][L][D] or NULL */
   const float *coef_pos, *coef_rot;          /* [T][3] posterior tables (see a3d_ddpm_step) */
+  /* the history term of a multistep schedule (DPM-Solver++ 2M, see a3d_ddpm_step_hist); all three NULL: none, today's arithmetic.
+   * hist: [B][L][D], read where kappa[row] != 0 and written by every non-terminal step; kappa_*: [n_rows] by step position.
+   * Only the schedule entries (a3d_dn_tail_sched, a3d_dn_persist_sched, a3d_dn_persist_group) accept them, all three or none. */
+  float* hist;
+  const float *kappa_pos, *kappa_rot;
 } a3d_dn_tail_params;
 int a3d_dn_head(const float* traj, int D, const a3d_dn_head_params* p, float* x_out, int B, int L, int E, int H, void* stream);
 size_t a3d_dn_cross_ws_floats(int B, int H, int nsplit);
