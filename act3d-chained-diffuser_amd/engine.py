@@ -608,73 +608,79 @@ def fwd_bwd_trajectory(model, criterion, sample, on_hot_done=None):
     return _split_backward(list(tokens) if multi else [tokens], hot, on_hot_done)
 
 
-def _finish_step(optimizer, ddp, step_id, accumulate_grad_batches):
-    if step_id % accumulate_grad_batches == accumulate_grad_batches - 1:
-        scale = ddp.sync_gradients() if ddp is not None else 1.0
-        optimizer.step(grad_scale=scale) if isinstance(optimizer, FlatAdamW) else optimizer.step()
+class EagerStep:
+    """The training-step protocol, written once: launch() is everything up to the point where the gradient reductions must have
+    finished -- zero_grad at the start of an accumulation window, arm the early reduction (only the window's final micro-batch may
+    start reducing its gradients early), `fwd_bwd(sample, on_hot_done)` with the backward split at the FPN tokens, and on the final
+    micro-batch begin_sync() (started, not awaited); finish() joins the reductions and takes the optimizer step with 1/world.
+    Whatever the caller enqueues between the two -- the other model's launch() in a JointStep -- hides the reductions.
+    GraphedStep is the same pair on captured graphs."""
+
+    def __init__(self, fwd_bwd, optimizer, ddp=None, accumulate=1):
+        self.fwd_bwd, self.optimizer, self.ddp, self.accumulate = fwd_bwd, optimizer, ddp, max(1, int(accumulate))
+        self.loss, self._last = None, True
+
+    def launch(self, sample, step_id=0):
+        if step_id % self.accumulate == 0:
+            self.optimizer.zero_grad()
+        self._last = step_id % self.accumulate == self.accumulate - 1
+        if self.ddp is not None:
+            self.ddp.arm(self._last)
+        self.loss = self.fwd_bwd(sample, None if self.ddp is None else self.ddp.hot_path_done)
+        if self.ddp is not None and self._last:
+            self.ddp.begin_sync()
+
+    def finish(self):
+        if self._last:
+            scale = self.ddp.finish_sync() if self.ddp is not None else 1.0
+            self.optimizer.step(grad_scale=scale) if isinstance(self.optimizer, FlatAdamW) else self.optimizer.step()
+        return self.loss
+
+    def __call__(self, sample, step_id=0):
+        self.launch(sample, step_id)
+        return self.finish()
 
 
 def train_one_step(model, criterion, optimizer, step_id, sample, ddp=None, accumulate_grad_batches=1,
                    use_ground_truth_position_for_sampling_train=True):
     """TrainTester.train_one_step for the keypose model (main_keypose.py:207-234): zero_grad, forward, loss, backward,
     (all-reduce, overlapped with the FPN backward), optimizer step.  Returns the detached total loss."""
-    if step_id % accumulate_grad_batches == 0:
-        optimizer.zero_grad()
-    last = step_id % accumulate_grad_batches == accumulate_grad_batches - 1
-    if ddp is not None:
-        ddp.arm(last)                       # only the window's final micro-batch may start reducing its gradients early
-    loss = fwd_bwd_keypose(model, criterion, sample, use_ground_truth_position_for_sampling_train,
-                           None if ddp is None else ddp.hot_path_done)
-    _finish_step(optimizer, ddp, step_id, accumulate_grad_batches)
-    return loss
+    return EagerStep(lambda s, cb: fwd_bwd_keypose(model, criterion, s, use_ground_truth_position_for_sampling_train, cb),
+                     optimizer, ddp, accumulate_grad_batches)(sample, step_id)
 
 
 def train_one_step_trajectory(model, criterion, optimizer, step_id, sample, ddp=None, accumulate_grad_batches=1):
     """TrainTester.train_one_step for the trajectory model (main_trajectory.py:177-204)."""
-    if step_id % accumulate_grad_batches == 0:
-        optimizer.zero_grad()
-    last = step_id % accumulate_grad_batches == accumulate_grad_batches - 1
-    if ddp is not None:
-        ddp.arm(last)
-    loss = fwd_bwd_trajectory(model, criterion, sample, None if ddp is None else ddp.hot_path_done)
-    _finish_step(optimizer, ddp, step_id, accumulate_grad_batches)
-    return loss
+    return EagerStep(lambda s, cb: fwd_bwd_trajectory(model, criterion, s, cb), optimizer, ddp, accumulate_grad_batches)(sample, step_id)
 
 
 class JointStep:
     """One joint iteration of BASELINE.json configs[3]: an Act3D keypose training step AND a trajectory-diffusion training
     step -- two models, two optimizers, as the reference trains them (main_keypose.py:207-234, main_trajectory.py:177-204),
-    each data-parallel over the same ranks (engine.py:121-124).
+    each data-parallel over the same ranks (engine.py:121-124).  `kp_step` / `tr_step` are any two launch() / finish() pairs:
+    EagerStep (JointStep.eager) or GraphedStep.
 
-    Order of one iteration:  keypose forward + backward (hot segments reduced early, FlatDataParallel.hot_path_done) ->
-    begin_sync() of its FPN segment on the side stream -> trajectory forward + backward ON THE MAIN STREAM, which hides the
-    keypose reductions -> trajectory reduction -> both AdamW steps.  The result is the same as running the two
-    train_one_step functions one after the other (tests/test_joint_gpu.py)."""
+    Order of one iteration:  keypose launch (forward + backward, hot segments reduced early, begin_sync() of its FPN segment on
+    the side stream) -> trajectory launch ON THE MAIN STREAM, which hides the keypose reductions -> both finish (join, AdamW).
+    The result is the same as running the two train_one_step functions one after the other (tests/test_joint_gpu.py)."""
 
-    def __init__(self, kp_model, kp_criterion, kp_optimizer, tr_model, tr_criterion, tr_optimizer, kp_ddp=None, tr_ddp=None,
-                 use_ground_truth_position_for_sampling_train=True):
-        self.kp = (kp_model, kp_criterion, kp_optimizer, kp_ddp)
-        self.tr = (tr_model, tr_criterion, tr_optimizer, tr_ddp)
-        self.use_gt = use_ground_truth_position_for_sampling_train
+    def __init__(self, kp_step, tr_step):
+        self.kp, self.tr = kp_step, tr_step
 
-    def __call__(self, kp_sample, tr_sample):
-        km, kc, ko, kd = self.kp
-        tm, tc, to, td = self.tr
-        ko.zero_grad()
-        to.zero_grad()
-        if kd is not None:
-            kd.arm(True)
-        loss_k = fwd_bwd_keypose(km, kc, kp_sample, self.use_gt, None if kd is None else kd.hot_path_done)
-        if kd is not None:
-            kd.begin_sync()
-        if td is not None:
-            td.arm(True)
-        loss_t = fwd_bwd_trajectory(tm, tc, tr_sample, None if td is None else td.hot_path_done)
-        if td is not None:
-            td.begin_sync()
-        ko.step(grad_scale=kd.finish_sync() if kd is not None else 1.0)
-        to.step(grad_scale=td.finish_sync() if td is not None else 1.0)
-        return loss_k, loss_t
+    @classmethod
+    def eager(cls, kp_model, kp_criterion, kp_optimizer, tr_model, tr_criterion, tr_optimizer, kp_ddp=None, tr_ddp=None,
+              use_ground_truth_position_for_sampling_train=True):
+        use_gt = use_ground_truth_position_for_sampling_train
+        return cls(EagerStep(lambda s, cb: fwd_bwd_keypose(kp_model, kp_criterion, s, use_gt, cb), kp_optimizer, kp_ddp),
+                   EagerStep(lambda s, cb: fwd_bwd_trajectory(tr_model, tr_criterion, s, cb), tr_optimizer, tr_ddp))
+
+    def __call__(self, kp_sample=None, tr_sample=None):
+        self.kp.launch(kp_sample)
+        self.tr.launch(tr_sample)
+        return self.kp.finish(), self.tr.finish()
+
+
+GraphedJointStep = JointStep          # JointStep over two GraphedSteps: the same four lines
 
 
 def save_checkpoint(path, model, optimizer, step_id, best_loss=None):
@@ -783,98 +789,97 @@ class GraphedStep:
         self.ddp = ddp
         self.world = ddp.world if ddp is not None else 1
         self.prefetch = prefetch
+        self.parity, self._primed, self._last = 0, False, 0
         split = self.world > 1
-        self.parity = 0
-        self._primed = False
-        sets = 1
-        gkw = {}
+        # one calling convention from here on, (inputs, cb): a world == 1 step function takes the inputs alone
+        self._step = step_fwd_bwd if split else (lambda inputs, cb: step_fwd_bwd(inputs))
+        self._graph_kw = {}
+        inputs = [dict(static_inputs)]
         if prefetch is not None:
-            sets = 2
             self.next_rgbs = static_inputs["rgbs"].clone()
             with torch.no_grad():
                 m0 = prefetch(static_inputs["rgbs"])
             self.maps = [m0, {k: torch.empty_like(v) for k, v in m0.items()}]
             self._pf_stream = torch.cuda.Stream(priority=-1) if PREFETCH_HIPRIO == "side" else torch.cuda.Stream()
             if PREFETCH_HIPRIO in ("1", "main"):     # capture stream above the prefetch stream: the hot path's short kernels dispatch first
-                gkw["stream"] = torch.cuda.Stream(priority=-1)
-        inputs = [dict(static_inputs) for _ in range(sets)]
-        if prefetch is not None:
-            for p_ in range(sets):
-                inputs[p_]["backbone_maps"] = self.maps[p_]
-        call = (lambda p_, cb: step_fwd_bwd(inputs[p_], cb)) if split else (lambda p_, cb: step_fwd_bwd(inputs[p_]))
+                self._graph_kw["stream"] = torch.cuda.Stream(priority=-1)
+            inputs = [dict(static_inputs, backbone_maps=m) for m in self.maps]
+        self._warm_up(inputs[0], warmup)
+        self.g_fb, self.g_late, self.loss, self.g_opt = [], [], [], None
+        pool = None                                  # shared by every graph of this step
+        for p_, inp in enumerate(inputs):
+            pool = (self._capture_split if split else self._capture_single)(p_, inp, pool)
+        if split:
+            self.g_opt = torch.cuda.CUDAGraph()
+            with self._capturing(self.g_opt, pool):
+                optimizer.step(grad_scale=1.0 / self.world)
+
+    def _warm_up(self, inputs, steps):
+        """`steps` eager steps on a side stream, so that every lazily created workspace / MIOpen plan exists before the capture"""
+        eager = EagerStep(self._step, self.optimizer, self.ddp)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(warmup):
-                optimizer.zero_grad()
-                call(0, ddp.hot_path_done if split else None)
-                scale = ddp.sync_gradients() if ddp is not None else 1.0
-                optimizer.step(grad_scale=scale)
+            for _ in range(steps):
+                eager(inputs)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
 
-        def fork(p_):
-            """the next batch's backbone on the side stream (joined by join()); no-op without prefetch"""
-            if prefetch is None:
-                return
-            self._pf_stream.wait_stream(torch.cuda.current_stream())
-            # the overlapped backbone's BatchNorm-apply passes with one workgroup per CU: the hot path's kernels find free wave slots
-            # (18.87 -> 18.45 ms per keypose step; grids are baked into the captured graph, so only this capture sees the setting)
-            lib = L.load()
-            prev = lib.a3d_bn_grid_cap(PREFETCH_BN_GRID) if PREFETCH_BN_GRID > 0 else 0
-            try:
-                with torch.cuda.stream(self._pf_stream), torch.no_grad():
-                    prefetch(self.next_rgbs, out=self.maps[1 - p_])
-            finally:
-                if PREFETCH_BN_GRID > 0:
-                    lib.a3d_bn_grid_cap(prev)
+    def _capturing(self, graph, pool):
+        return torch.cuda.graph(graph, pool=pool, **self._graph_kw)
 
-        def join():
-            if prefetch is not None:
-                torch.cuda.current_stream().wait_stream(self._pf_stream)
+    def _fork_prefetch(self, p_):
+        """the next batch's backbone on the side stream (joined by _join_prefetch()); no-op without prefetch"""
+        if self.prefetch is None:
+            return
+        self._pf_stream.wait_stream(torch.cuda.current_stream())
+        # the overlapped backbone's BatchNorm-apply passes with one workgroup per CU: the hot path's kernels find free wave slots
+        # (18.87 -> 18.45 ms per keypose step; grids are baked into the captured graph, so only this capture sees the setting)
+        lib = L.load()
+        prev = lib.a3d_bn_grid_cap(PREFETCH_BN_GRID) if PREFETCH_BN_GRID > 0 else 0
+        try:
+            with torch.cuda.stream(self._pf_stream), torch.no_grad():
+                self.prefetch(self.next_rgbs, out=self.maps[1 - p_])
+        finally:
+            if PREFETCH_BN_GRID > 0:
+                lib.a3d_bn_grid_cap(prev)
 
-        self.g_fb, self.g_late, self.loss = [], [], []
-        self.g_opt = None
-        pool = None
-        for p_ in range(sets):
-            g = torch.cuda.CUDAGraph()
-            self.g_fb.append(g)
-            if not split:
-                with (torch.cuda.graph(g, **gkw) if pool is None else torch.cuda.graph(g, pool=pool, **gkw)):
-                    fork(p_)
-                    optimizer.zero_grad()
-                    self.loss.append(call(p_, None))
-                    optimizer.step(grad_scale=1.0)
-                    join()
-                pool = g.pool()
-                continue
-            # world > 1: the capture of the first graph ends inside the callback (hot path done), the second one starts there
-            g2 = torch.cuda.CUDAGraph()
-            self.g_late.append(g2)
-            ctx = {}
+    def _join_prefetch(self):
+        if self.prefetch is not None:
+            torch.cuda.current_stream().wait_stream(self._pf_stream)
+
+    def _capture_single(self, p_, inputs, pool):
+        """world == 1: ONE graph [prefetch fork + zero_grad + forward + loss + backward + AdamW + prefetch join].  Returns the pool."""
+        g = torch.cuda.CUDAGraph()
+        self.g_fb.append(g)
+        with self._capturing(g, pool):
+            self._fork_prefetch(p_)
+            self.optimizer.zero_grad()
+            self.loss.append(self._step(inputs, None))
+            self.optimizer.step(grad_scale=1.0)
+            self._join_prefetch()
+        return g.pool()
+
+    def _capture_split(self, p_, inputs, pool):
+        """world > 1: the capture of the first graph ends inside the step function's callback (hot path done, prefetch joined: the
+        prefetched backbone overlaps the forward + hot-path backward), the second one starts there.  Returns the pool."""
+        g, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        self.g_fb.append(g)
+        self.g_late.append(g2)
+        with contextlib.ExitStack() as capture:
+            capture.enter_context(self._capturing(g, pool))
+            # unwound before the first capture ends -- at the split point, or by a step function that raises before reaching it: no
+            # capture is left open and the side stream is not left unjoined
+            capture.callback(self._join_prefetch)
 
             def switch_graphs():
-                join()                               # the prefetched backbone overlaps the forward + hot-path backward
-                ctx["first"].__exit__(None, None, None)
-                ctx["second"] = torch.cuda.graph(g2, pool=g.pool() if pool is None else pool, **gkw)
-                ctx["second"].__enter__()
+                capture.close()
+                capture.enter_context(self._capturing(g2, g.pool() if pool is None else pool))
 
-            ctx["first"] = torch.cuda.graph(g, **gkw) if pool is None else torch.cuda.graph(g, pool=pool, **gkw)
-            ctx["first"].__enter__()
-            try:
-                fork(p_)
-                optimizer.zero_grad()
-                self.loss.append(call(p_, switch_graphs))
-            finally:
-                if "second" not in ctx:
-                    join()                           # a step that never reached its split point: do not leave the side stream unjoined
-                (ctx.get("second") or ctx["first"]).__exit__(None, None, None)
-            pool = g.pool()
-        if split:
-            self.g_opt = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_opt, pool=pool, **gkw):
-                optimizer.step(grad_scale=1.0 / self.world)
-        self._last = 0
+            self._fork_prefetch(p_)
+            self.optimizer.zero_grad()
+            self.loss.append(self._step(inputs, switch_graphs))
+        return g.pool()
 
     def launch(self, inputs=None, next_rgbs=None):
         """Enqueue the step up to (not including) the point where the gradient reductions must have finished: input copies,
@@ -916,17 +921,3 @@ class GraphedStep:
     def __call__(self, inputs=None, next_rgbs=None):
         self.launch(inputs, next_rgbs)
         return self.finish()
-
-
-class GraphedJointStep:
-    """JointStep on captured graphs: one GraphedStep per model; the keypose reductions are started before the trajectory
-    graphs are replayed and awaited after them, so the trajectory forward / backward hides them (same order of operations as
-    JointStep.__call__)."""
-
-    def __init__(self, keypose_step, trajectory_step):
-        self.kp, self.tr = keypose_step, trajectory_step
-
-    def __call__(self, kp_sample=None, tr_sample=None):
-        self.kp.launch(kp_sample)
-        self.tr.launch(tr_sample)
-        return self.kp.finish(), self.tr.finish()

@@ -4,10 +4,12 @@ API contract (names, arguments, return values): `BaseTrainTester` <-> `engine.py
 `main_keypose.py:97-281` (`TrainTester`), `TrajectoryTrainTester` <-> `main_trajectory.py:86-274`; `args` is any namespace
 with the reference's `Arguments` fields.  The machinery underneath is this package's own:
 
-  StepRunner   owns (model, criterion, optimizer, ddp) and a small set of captured hipGraphs keyed by the batch signature:
-               the second time a batch shape shows up its whole step (zero_grad + forward + loss + backward [+ the
-               all-reduces between three graphs under DP] + fused AdamW) is captured (engine.GraphedStep) and from then on
-               replayed -- `main()` therefore runs what `bench.py` times; odd shapes and gradient accumulation run eagerly.
+  StepRunner   owns (model, optimizer, ddp), the family's split forward / backward and a small set of captured hipGraphs keyed
+               by the batch signature: the second time a batch shape shows up its whole step (zero_grad + forward + loss +
+               backward [+ the all-reduces between three graphs under DP] + fused AdamW) is captured (engine.GraphedStep) and
+               from then on replayed -- `main()` runs the SEQUENTIAL graph, without the next batch's backbone prefetched into it
+               (GraphedStep(prefetch=...), which is what `bench.py` times); odd shapes, gradient accumulation and eval mode run
+               the eager step (engine.EagerStep).
   MetricTable  evaluation statistics as (sum, count) per key on the device: one row per batch, per-task rows through a group
                mask, ranks combined with ONE all-reduce of the table (the reference gathers python dicts of growing tensors).
   _Schedule    the iteration plan (what happens after step i) as data instead of inline modulo tests.
@@ -147,45 +149,44 @@ def _signature(sample):
 
 
 class StepRunner:
-    """Runs training steps for one (model, criterion, optimizer[, ddp]): captured hipGraph replays for batch shapes that
-    recur, the eager engine step otherwise.  `fwd_bwd(model, criterion, sample, on_hot_done)` is the split forward /
-    backward of the model family (engine.fwd_bwd_keypose / fwd_bwd_trajectory); `eager_step(step_id, sample)` the full eager
-    step incl. gradient accumulation."""
+    """Runs training steps for one (model, optimizer[, ddp]): captured hipGraph replays for batch shapes that recur, the
+    eager engine step (engine.EagerStep, incl. gradient accumulation) otherwise.  `fwd_bwd(sample, on_hot_done)` is the split
+    forward / backward of the model family (engine.fwd_bwd_keypose / fwd_bwd_trajectory) bound to its model and criterion."""
 
-    def __init__(self, model, criterion, optimizer, ddp, fwd_bwd, eager_step, accumulate=1, max_graphs=4, enable=True):
-        self.model, self.criterion, self.optimizer, self.ddp = model, criterion, optimizer, ddp
-        self.fwd_bwd, self.eager_step = fwd_bwd, eager_step
-        self.accumulate = max(1, int(accumulate))
+    def __init__(self, model, optimizer, ddp, fwd_bwd, accumulate=1, max_graphs=4, enable=True):
+        self.model, self.optimizer, self.ddp, self.fwd_bwd = model, optimizer, ddp, fwd_bwd
+        self.eager = E.EagerStep(fwd_bwd, optimizer, ddp, accumulate=accumulate)
         self.max_graphs = max_graphs
-        self.enable = enable and self.accumulate == 1 and os.environ.get("A3D_TRAINER_GRAPHS", "1") == "1"
+        self.enable = enable and self.eager.accumulate == 1 and os.environ.get("A3D_TRAINER_GRAPHS", "1") == "1"
         self._seen = {}
         self._graphs = {}
         self.replays = 0
 
     def _capture(self, sample):
         static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in sample.items()}
-        fb = (lambda s, cb=None: self.fwd_bwd(self.model, self.criterion, s, cb)) if self.ddp is not None and self.ddp.world > 1 \
-            else (lambda s: self.fwd_bwd(self.model, self.criterion, s, None))
+        if self.ddp is not None and self.ddp.world > 1:
+            fb, ddp = self.fwd_bwd, self.ddp
+        else:
+            fb, ddp = (lambda s: self.fwd_bwd(s, None)), None
         # warmup = 0: an eager step with exactly these shapes has already run (first sighting), so every lazily created
         # workspace / MIOpen plan exists and no optimizer step is spent on warm-up replays of one batch
-        return E.GraphedStep(fb, self.optimizer, static, ddp=self.ddp if (self.ddp is not None and self.ddp.world > 1) else None,
-                             warmup=0)
+        return E.GraphedStep(fb, self.optimizer, static, ddp=ddp, warmup=0)
 
     def __call__(self, step_id, sample):
         if not self.enable or not self.model.training:
-            return self.eager_step(step_id, sample)
+            return self.eager(sample, step_id)
         sig = _signature(sample)
         graph = self._graphs.get(sig)
         if graph is None:
             self._seen[sig] = self._seen.get(sig, 0) + 1
             if self._seen[sig] < 2 or len(self._graphs) >= self.max_graphs:
-                return self.eager_step(step_id, sample)
+                return self.eager(sample, step_id)
             try:
                 graph = self._graphs[sig] = self._capture(sample)
             except Exception as exc:                      # a shape that cannot be captured keeps running eagerly, loudly
                 print(f"[StepRunner] graph capture failed for {sig[:2]}...: {exc!r}; this shape runs eagerly")
                 self._seen[sig] = -(1 << 30)
-                return self.eager_step(step_id, sample)
+                return self.eager(sample, step_id)
         self.replays += 1
         return graph(sample)
 
@@ -237,16 +238,14 @@ def _lr_schedule(a):
 
 
 class BaseTrainTester:
-    """The driver skeleton.  Subclasses say what the datasets, the model, the criterion, one training step and one
-    evaluation round are; `main` wires loaders -> model -> optimizer -> (DP) -> resume -> the scheduled loop."""
-
-    split_fwd_bwd = None            # engine.fwd_bwd_* of the model family (set by the subclass)
+    """The driver skeleton.  Subclasses say what the datasets, the model, the criterion, the forward / backward of one training
+    step and one evaluation round are; `main` wires loaders -> model -> optimizer -> (DP) -> resume -> the scheduled loop."""
 
     def __init__(self, args):
         self.args = args
         self.writer = _Scalars(getattr(args, "log_dir", None)) if get_rank() == 0 else None
         self.ddp = None
-        self._runner = None
+        self._runner = self._runner_key = None      # the StepRunner of the last (model, criterion, optimizer) seen
 
     @property
     def scalars(self):
@@ -266,8 +265,9 @@ class BaseTrainTester:
     def get_criterion(self):
         return None
 
-    def train_one_step(self, model, criterion, optimizer, step_id, sample):
-        pass
+    def fwd_bwd(self, model, criterion, sample, on_hot_done):
+        """engine.fwd_bwd_* of the model family: forward + loss + backward split at the FPN tokens; returns the detached loss"""
+        raise NotImplementedError
 
     @torch.no_grad()
     def evaluate_nsteps(self, model, criterion, loader, step_id, val_iters, split='val'):
@@ -345,12 +345,16 @@ class BaseTrainTester:
                     best_loss = self.save_checkpoint(model, optimizer, step_id, new_loss, best_loss)
         return model
 
-    def _runner_for(self, model, criterion, optimizer, eager_step):
-        r = self._runner
-        if r is None or r.model is not model or r.optimizer is not optimizer or r.criterion is not criterion:
-            r = self._runner = StepRunner(model, criterion, optimizer, self.ddp, type(self).split_fwd_bwd, eager_step,
-                                          accumulate=getattr(self.args, "accumulate_grad_batches", 1))
-        return r
+    def train_one_step(self, model, criterion, optimizer, step_id, sample):
+        """One training step through the StepRunner of (model, criterion, optimizer); returns the detached loss."""
+        key = (model, criterion, optimizer)
+        if self._runner is None or any(a is not b for a, b in zip(self._runner_key, key)):
+            self._runner_key = key
+            self._runner = StepRunner(model, optimizer, self.ddp, lambda s, cb: self.fwd_bwd(model, criterion, s, cb),
+                                      accumulate=getattr(self.args, "accumulate_grad_batches", 1))
+        loss = self._runner(step_id, sample)
+        self._log_train(loss, step_id, optimizer)
+        return loss
 
     def _log_train(self, loss, step_id, optimizer=None):
         if self.writer is not None and (step_id + 1) % self.args.val_freq == 0:
@@ -426,9 +430,8 @@ def _datasets(a, trajectories):
 class KeyposeTrainTester(BaseTrainTester):
     """Act3D keypose training / evaluation (main_keypose.py:97-281)."""
 
-    @staticmethod
-    def split_fwd_bwd(model, criterion, sample, cb, use_gt=True):
-        return E.fwd_bwd_keypose(model, criterion, sample, use_gt, cb)
+    def fwd_bwd(self, model, criterion, sample, on_hot_done):
+        return E.fwd_bwd_keypose(model, criterion, sample, bool(self.args.use_ground_truth_position_for_sampling_train), on_hot_done)
 
     def get_datasets(self):
         return _datasets(self.args, trajectories=False)
@@ -458,21 +461,6 @@ class KeyposeTrainTester(BaseTrainTester):
                               rotation_loss_coeff=a.rotation_loss_coeff, gripper_loss_coeff=a.gripper_loss_coeff,
                               symmetric_rotation_loss=bool(a.symmetric_rotation_loss))
 
-    def train_one_step(self, model, criterion, optimizer, step_id, sample):
-        use_gt = bool(self.args.use_ground_truth_position_for_sampling_train)
-
-        def eager(i, s):
-            return E.train_one_step(model, criterion, optimizer, i, s, ddp=self.ddp,
-                                    accumulate_grad_batches=self.args.accumulate_grad_batches,
-                                    use_ground_truth_position_for_sampling_train=use_gt)
-
-        runner = self._runner_for(model, criterion, optimizer, eager)
-        runner.fwd_bwd = lambda m, c, s, cb: E.fwd_bwd_keypose(m, c, s, use_gt, cb)
-        runner.eager_step = eager
-        loss = runner(step_id, sample)
-        self._log_train(loss, step_id, optimizer)
-        return loss
-
     @torch.no_grad()
     def evaluate_nsteps(self, model, criterion, loader, step_id, val_iters, split='val'):
         """Free-running forward (no ground-truth anchor for the ghost points) over `val_iters` batches; every metric of
@@ -493,9 +481,8 @@ class KeyposeTrainTester(BaseTrainTester):
 class TrajectoryTrainTester(BaseTrainTester):
     """ChainedDiffuser trajectory-diffusion training / evaluation (main_trajectory.py:86-274)."""
 
-    @staticmethod
-    def split_fwd_bwd(model, criterion, sample, cb):
-        return E.fwd_bwd_trajectory(model, criterion, sample, cb)
+    def fwd_bwd(self, model, criterion, sample, on_hot_done):
+        return E.fwd_bwd_trajectory(model, criterion, sample, on_hot_done)
 
     def get_datasets(self):
         return _datasets(self.args, trajectories=True)
@@ -515,17 +502,6 @@ class TrajectoryTrainTester(BaseTrainTester):
     @staticmethod
     def get_criterion():
         return TrajectoryCriterion()
-
-    def train_one_step(self, model, criterion, optimizer, step_id, sample):
-        def eager(i, s):
-            return E.train_one_step_trajectory(model, criterion, optimizer, i, s, ddp=self.ddp,
-                                               accumulate_grad_batches=self.args.accumulate_grad_batches)
-
-        runner = self._runner_for(model, criterion, optimizer, eager)
-        runner.eager_step = eager
-        loss = runner(step_id, sample)
-        self._log_train(loss, step_id, optimizer)
-        return loss
 
     @torch.no_grad()
     def evaluate_nsteps(self, model, criterion, loader, step_id, val_iters, split='val'):

@@ -174,7 +174,7 @@ def _worker(rank, world, port, mode, q):
             g = tflat.grad / world
         elif joint:
             # JointStep with the keypose forward teacher-forced: same object, the keypose fwd + bwd swapped for the smooth one
-            js = E.JointStep(kp, kcrit, kopt, tr, tcrit, topt, kp_ddp=kddp, tr_ddp=tddp)
+            js = E.JointStep.eager(kp, kcrit, kopt, tr, tcrit, topt, kp_ddp=kddp, tr_ddp=tddp)
             orig = E.fwd_bwd_keypose
             E.fwd_bwd_keypose = lambda model, crit, sample, use_gt, cb: _kp_fwd_bwd_tf(E, model, crit, sample, cb)
             try:
@@ -254,7 +254,7 @@ def test_joint_iteration_equals_the_two_steps_run_separately(a3d, dev):
     (kfA, koA), (kfB, koB) = E.get_optimizer(kA, lr=1e-4), E.get_optimizer(kB, lr=1e-4)
     (tfA, toA), (tfB, toB) = E.get_optimizer(tA, lr=1e-4), E.get_optimizer(tB, lr=1e-4)
     assert torch.equal(kfA.flat, kfB.flat) and torch.equal(tfA.flat, tfB.flat)
-    joint = E.JointStep(kA, kcrit, koA, tA, tcrit, toA)
+    joint = E.JointStep.eager(kA, kcrit, koA, tA, tcrit, toA)
     # both paths call engine.fwd_bwd_keypose; teacher-force its k-NN centres (the untrained model's argmax cascade turns
     # accumulation-order noise into a different context -- not what this test is about)
     orig = E.fwd_bwd_keypose
