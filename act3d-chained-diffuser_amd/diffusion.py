@@ -1042,7 +1042,7 @@ class DiffusionHead(nn.Module):
         out = traj.clone()
         self._last_persist = ps                      # tests read the abort word (sync[2]) after synchronising
         nt, npos, nrot = ps["stacks"]
-        common = (ps["table"].data_ptr(), nt, npos, nrot, O.C_byref(hp), O.C_byref(tp), out.data_ptr(), ps["qbuf"].data_ptr(),
+        common = (ps["table"].data_ptr(), nt, npos, nrot, Lb.byref(hp), Lb.byref(tp), out.data_ptr(), ps["qbuf"].data_ptr(),
                   ps["part"].data_ptr(), None if ps["kvx"] is None else ps["kvx"].data_ptr(), ps["xbuf"].data_ptr(), ps["sync"].data_ptr(),
                   B, Ln, D, st["sem"].shape[-1], self.num_attn_heads, st["S"], st["Sp"], ps["nsplit"], int(first), int(nsteps))
         if not isinstance(tables, SamplerSchedule):
@@ -1078,15 +1078,15 @@ class DiffusionHead(nn.Module):
         new = lambda: torch.empty((B, Ln, E), device=dev, dtype=torch.float32)
         hp = self._dn_head_params(st)
         x = new()
-        Lb.call("a3d_dn_head", traj.data_ptr(), D, O.C_byref(hp), x.data_ptr(), B, Ln, E, H, Lb.stream())
+        Lb.call("a3d_dn_head", traj.data_ptr(), D, Lb.byref(hp), x.data_ptr(), B, Ln, E, H, Lb.stream())
 
         def run_layer(xin, rec, ws):
             stream = Lb.stream()
             cp, rp = self._dn_cross_params(st, rec, row), self._dn_rest_params(st, rec, row)
-            Lb.call("a3d_dn_cross", xin.data_ptr(), traj.data_ptr(), D, O.C_byref(cp), ws.data_ptr(), B, Ln, E, H, st["S"],
+            Lb.call("a3d_dn_cross", xin.data_ptr(), traj.data_ptr(), D, Lb.byref(cp), ws.data_ptr(), B, Ln, E, H, st["S"],
                     st["Sp"], st["nsplit"], stream)
             xout = new()
-            Lb.call("a3d_dn_rest", xin.data_ptr(), traj.data_ptr(), D, ws.data_ptr(), O.C_byref(rp), xout.data_ptr(), B, Ln,
+            Lb.call("a3d_dn_rest", xin.data_ptr(), traj.data_ptr(), D, ws.data_ptr(), Lb.byref(rp), xout.data_ptr(), B, Ln,
                     E, H, st["nsplit"], stream)
             return xout
 
@@ -1111,7 +1111,7 @@ class DiffusionHead(nn.Module):
         cur.wait_stream(side)
         rf.record_stream(cur)
         tp = self._dn_tail_params(noise, cond_data, cond_mask_u8, tables, st.get("hist"))
-        tail = (pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, O.C_byref(tp), out.data_ptr(), B, Ln, E, int(row))
+        tail = (pf.data_ptr(), rf.data_ptr(), traj.data_ptr(), D, Lb.byref(tp), out.data_ptr(), B, Ln, E, int(row))
         if not isinstance(tables, SamplerSchedule):
             Lb.call("a3d_dn_tail", *tail, Lb.stream())
         else:

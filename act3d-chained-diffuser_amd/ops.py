@@ -372,11 +372,10 @@ def write_operands(f16, groups, role, slots, freq, B, E, H, device, x=None, wp=N
     fused: one a3d_proj_rope_split[16] per group (blk0, blk1 = the group's roles).  Else one linear launch per group, then one
     a3d_rope_split[16] per role on its column slice; pre = {role: (pointer, leading dimension)} names rows that are projected already."""
     st, fp = L.stream(), freq.data_ptr()
-    nz = lambda t: None if t is None else t.data_ptr()
 
     def blk(r):                                  # a role's launch arguments: xyz, scale, its slot in the family's order
-        xyz, scale, s = nz(role[r].xyz), role[r].scale, slots[r]
-        return (xyz, scale, nz(s.rows), nz(s.planes), s.word) if f16 else (xyz, scale, nz(s.rows), s.word, nz(s.planes))
+        xyz, scale, s = L.nz(role[r].xyz), role[r].scale, slots[r]
+        return (xyz, scale, L.nz(s.rows), L.nz(s.planes), s.word) if f16 else (xyz, scale, L.nz(s.rows), s.word, L.nz(s.planes))
 
     if fused:
         absent = (None, 1.0, None, None, 1) if f16 else (None, 1.0, None, 32, None)
@@ -1028,17 +1027,16 @@ class SingleQueryAttnBlockFn(torch.autograd.Function):
         freq = rope_freq(E, dev)
         scale = float(E // H) ** -0.5
         wp, bp = in_w.data_ptr(), in_b.data_ptr()
-        nz = lambda t: None if t is None else t.data_ptr()
         q_pre = linear_raw(q_in.data_ptr(), E, wp, E, bp, B, E, E, dev)
         qrot = torch.empty((B, H, 1, 16), device=dev, dtype=F32)
-        L.call("a3d_rope_rows_f32", q_pre.data_ptr(), E, nz(q_xyz), freq.data_ptr(), scale, qrot.data_ptr(), B, 1, 1, E, H, L.stream())
+        L.call("a3d_rope_rows_f32", q_pre.data_ptr(), E, L.nz(q_xyz), freq.data_ptr(), scale, qrot.data_ptr(), B, 1, 1, E, H, L.stream())
         nsplit = sq_nsplit(B, S)
         lib = L.load()
         ws = torch.empty((lib.a3d_sq_fwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)
         xbar = torch.empty((B, H, E), device=dev, dtype=F32)
         lse = torch.empty((B, H), device=dev, dtype=F32)
         o = torch.empty((B, E), device=dev, dtype=F32)
-        L.call("a3d_sq_attn_fwd", kv_in.data_ptr(), nz(k_xyz), wp + E * E * f4, E, bp + E * f4, wp + 2 * E * E * f4, E,
+        L.call("a3d_sq_attn_fwd", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, wp + 2 * E * E * f4, E,
                bp + 2 * E * f4, qrot.data_ptr(), freq.data_ptr(), ws.data_ptr(), xbar.data_ptr(), lse.data_ptr(), o.data_ptr(), B, S, E,
                H, nsplit, L.stream())
         Y = linear2d(o, out_w, out_b)
@@ -1060,7 +1058,6 @@ class SingleQueryAttnBlockFn(torch.autograd.Function):
         if not has_xyz:
             q_xyz = k_xyz = None
         freq = rope_freq(E, dev)
-        nz = lambda t: None if t is None else t.data_ptr()
         dS = add_layernorm_bwd(resid.view(B, E), Y, ln_g, ln_b, mean, rstd, _c(dy).view(B, E))
         dO = dgrad2d(dS, out_w)
         wgrad2d(dS, o, out_w, out_b)
@@ -1070,7 +1067,7 @@ class SingleQueryAttnBlockFn(torch.autograd.Function):
         ws = torch.empty((lib.a3d_sq_bwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)
         dX = torch.empty((B, S, E), device=dev, dtype=F32)
         dqp = torch.empty((nsplit, B, H, 1, 16), device=dev, dtype=F32)
-        L.call("a3d_sq_attn_bwd", kv_in.data_ptr(), nz(k_xyz), wp + E * E * f4, E, bp + E * f4, wp + 2 * E * E * f4, E, qrot.data_ptr(),
+        L.call("a3d_sq_attn_bwd", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, wp + 2 * E * E * f4, E, qrot.data_ptr(),
                freq.data_ptr(), xbar.data_ptr(), lse.data_ptr(), dO.data_ptr(), ws.data_ptr(), dX.data_ptr(), dqp.data_ptr(),
                gW.data_ptr() + E * E * f4, E, gb.data_ptr() + E * f4, gW.data_ptr() + 2 * E * E * f4, E, gb.data_ptr() + 2 * E * f4,
                B, S, E, H, nsplit, L.stream())
@@ -1104,21 +1101,20 @@ class QueryLayerFn(torch.autograd.Function):
         freq = rope_freq(E, dev)
         scale = float(E // H) ** -0.5
         wp, bp = in_w.data_ptr(), in_b.data_ptr()
-        nz = lambda t: None if t is None else t.data_ptr()
         st = L.stream()
         lib = L.load()
         qrot = torch.empty((B, H, 1, 16), device=dev, dtype=F32)
-        L.call("a3d_qs_pre_fwd", x.data_ptr(), wp, bp, nz(q_xyz), freq.data_ptr(), scale, qrot.data_ptr(), B, E, H, st)
+        L.call("a3d_qs_pre_fwd", x.data_ptr(), wp, bp, L.nz(q_xyz), freq.data_ptr(), scale, qrot.data_ptr(), B, E, H, st)
         nsplit = sq_nsplit(B, S)
         ws = torch.empty((lib.a3d_sq_fwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)
         xbar = torch.empty((B, H, E), device=dev, dtype=F32)
         lse = torch.empty((B, H), device=dev, dtype=F32)
-        L.call("a3d_sq_attn_fwd", kv_in.data_ptr(), nz(k_xyz), wp + E * E * f4, E, bp + E * f4, None, E, None, qrot.data_ptr(),
+        L.call("a3d_sq_attn_fwd", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, None, E, None, qrot.data_ptr(),
                freq.data_ptr(), ws.data_ptr(), xbar.data_ptr(), lse.data_ptr(), None, B, S, E, H, nsplit, st)
         save = torch.empty((lib.a3d_qs_save_floats(B, E),), device=dev, dtype=F32)
         y = torch.empty((B, 1, E), device=dev, dtype=F32)
         qp = QueryLayerFn._params(in_w, in_b, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2, E)
-        L.call("a3d_qs_post_fwd", xbar.data_ptr(), x.data_ptr(), C_byref(qp), save.data_ptr(), y.data_ptr(), B, E, H, st)
+        L.call("a3d_qs_post_fwd", xbar.data_ptr(), x.data_ptr(), L.byref(qp), save.data_ptr(), y.data_ptr(), B, E, H, st)
         ctx.save_for_backward(x, kv_in, qrot, xbar, lse, save,
                               q_xyz if q_xyz is not None else torch.empty(0, device=dev),
                               k_xyz if k_xyz is not None else torch.empty(0, device=dev))
@@ -1144,7 +1140,6 @@ class QueryLayerFn(torch.autograd.Function):
         if not has_xyz:
             q_xyz = k_xyz = None
         freq = rope_freq(E, dev)
-        nz = lambda t: None if t is None else t.data_ptr()
         st = L.stream()
         lib = L.load()
         gW, gb = grad_buf(in_w), grad_buf(in_b)
@@ -1156,25 +1151,20 @@ class QueryLayerFn(torch.autograd.Function):
                        dg2=grad_buf(g2).data_ptr(), db2=grad_buf(b2).data_ptr())
         ws = torch.empty((lib.a3d_sq_bwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)    # dxbar | cD | weight-gradient partials
         dx = torch.empty((B, 1, E), device=dev, dtype=F32)
-        L.call("a3d_qs_post_bwd", _c(dy).data_ptr(), x.data_ptr(), xbar.data_ptr(), save.data_ptr(), C_byref(qp), C_byref(gr),
+        L.call("a3d_qs_post_bwd", _c(dy).data_ptr(), x.data_ptr(), xbar.data_ptr(), save.data_ptr(), L.byref(qp), L.byref(gr),
                ws.data_ptr(), ws.data_ptr() + B * H * E * f4, dx.data_ptr(), B, E, H, st)
         dqp = torch.empty((nsplit, B, H, 1, 16), device=dev, dtype=F32)
         if ctx.sink is not None:
             dXb, acc = ctx.sink.begin()                      # the context's shared gradient buffer: written or summed into
         else:
             dXb, acc = torch.empty((B, S, E), device=dev, dtype=F32), False
-        L.call("a3d_sq_attn_bwd_acc", kv_in.data_ptr(), nz(k_xyz), wp + E * E * f4, E, bp + E * f4, None, E, qrot.data_ptr(),
+        L.call("a3d_sq_attn_bwd_acc", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, None, E, qrot.data_ptr(),
                freq.data_ptr(), xbar.data_ptr(), lse.data_ptr(), None, ws.data_ptr(), dXb.data_ptr(), dqp.data_ptr(),
                gW.data_ptr() + E * E * f4, E, gb.data_ptr() + E * f4, None, E, None, B, S, E, H, nsplit, 1 if acc else 0, st)
         dX = ctx.sink.end() if ctx.sink is not None else dXb
-        L.call("a3d_qs_pre_bwd", dqp.data_ptr(), nsplit, nz(q_xyz), freq.data_ptr(), scale, x.data_ptr(), wp, gW.data_ptr(), gb.data_ptr(),
+        L.call("a3d_qs_pre_bwd", dqp.data_ptr(), nsplit, L.nz(q_xyz), freq.data_ptr(), scale, x.data_ptr(), wp, gW.data_ptr(), gb.data_ptr(),
                dx.data_ptr(), B, E, H, st)
         return (dx if ctx.needs_input_grad[0] else None, dX if ctx.needs_input_grad[1] else None) + (None,) * 16
-
-
-def C_byref(struct):
-    import ctypes
-    return ctypes.byref(struct)
 
 
 def query_layer_applicable(query, value, E, H, hidden):
