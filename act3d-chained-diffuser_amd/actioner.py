@@ -21,7 +21,7 @@ import torch
 from .diffusion import check_sampling_call, _graph_replay
 
 _TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight",
-            "scene_mask", "clear_margin", "clear_skip", "guide", "solver_order", "lower_order_final")
+            "scene_mask", "clear_margin", "clear_skip", "guide", "solver_order", "lower_order_final", "pins")
 
 
 def _same_tensors(a, b):
@@ -88,6 +88,7 @@ class Actioner:
         self._graph = None
         self.last_backbone_passes = 0
         self.last_ranking = None
+        self.last_pins = None
         if predict_keypose:
             keypose_model.eval()
         if predict_trajectory:
@@ -233,9 +234,10 @@ class Actioner:
         (B, history, >= action_dim), read only with predict_keypose=False; trajectory_mask (B, L), needed with
         predict_trajectory=True.  Returns {"action": (B, 8) or gt_action[:, -1], "trajectory": compute_trajectory's result or None,
         "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps, select,
-        rot_weight, scene_mask, clear_margin, clear_skip, guide, solver_order, lower_order_final) go to compute_trajectory unchanged (a rule that weighs "clearance"
+        rot_weight, scene_mask, clear_margin, clear_skip, guide, solver_order, lower_order_final, pins) go to compute_trajectory unchanged (a rule that weighs "clearance"
         scores the candidates against pcds[:, -1], and `guide` steers the waypoints off that cloud while they are drawn); with select the candidates are ranked on the device, "trajectory" is the
-        selected one (B, L, 8) and self.last_ranking mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
+        selected one (B, L, 8) and self.last_ranking mirrors the planner's; with pins (diffusion.check_pins, pose rows of action_dim
+        channels; diffusion.prefix_pins for a replan that keeps what the robot is executing) self.last_pins mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
         and the sampling loop as graphs."""
         bad = [k for k in sample_kw if k not in _TRAJ_KW]
         if bad:
@@ -245,6 +247,8 @@ class Actioner:
                 raise ValueError("select ranks sampled trajectories: it needs predict_trajectory=True")
             if sample_kw.get("guide") is not None:
                 raise ValueError("guide steers sampled trajectories: it needs predict_trajectory=True")
+            if sample_kw.get("pins") is not None:
+                raise ValueError("pins are waypoints of sampled trajectories: they need predict_trajectory=True")
         self._check(rgbs, pcds, gripper, gt_action, trajectory_mask, use_graph, ghost_points)
         if self._predict_trajectory:
             # the sampling call's own argument errors, before the keypose half launches anything (the schedule and the noise
@@ -279,6 +283,7 @@ class Actioner:
             passes += 0 if tokens is not None else 1
             if sample_kw.get("select") is not None:
                 self.last_ranking = self._traj_model.last_ranking
+            self.last_pins = self._traj_model.last_pins
         else:
             output["trajectory"] = None
         self.last_backbone_passes = passes

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(PKG_DIR, _OUT)
 if _OUT != "libact3d_hip.so":
     OBJ_DIR = os.path.join(CSRC, "obj_" + _OUT[len("libact3d_hip_"):-3])
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
-SOURCES = ["api.hip", "linear.hip", "linear_split.hip", "rope.hip", "ctx_proj.hip", "attention.hip", "attention_bwd.hip", "attention16.hip", "attention8.hip", "scene.hip", "heads.hip", "optim.hip", "diffusion.hip", "traj_rank.hip", "traj_clearance.hip", "traj_guide.hip", "vision.hip", "dropout.hip", "denoise.hip", "single_query.hip", "single_query_wave.hip", "query_stream.hip", "data.hip", "conv1x1.hip", "conv1x1_deep.hip", "bn_gram.hip", "conv3x3.hip", "fpn_sparse.hip", "stem.hip"]
+SOURCES = ["api.hip", "linear.hip", "linear_split.hip", "rope.hip", "ctx_proj.hip", "attention.hip", "attention_bwd.hip", "attention16.hip", "attention8.hip", "scene.hip", "heads.hip", "optim.hip", "diffusion.hip", "traj_rank.hip", "traj_clearance.hip", "traj_guide.hip", "traj_pins.hip", "vision.hip", "dropout.hip", "denoise.hip", "single_query.hip", "single_query_wave.hip", "query_stream.hip", "data.hip", "conv1x1.hip", "conv1x1_deep.hip", "bn_gram.hip", "conv3x3.hip", "fpn_sparse.hip", "stem.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # The attention kernels never produce NaNs on their own (masked rows are handled explicitly, -inf only enters exp2):
 # without IEEE-mode sNaN quieting hipcc drops the canonicalising v_max_f32 x, x it otherwise puts in front of every fmaxf
@@ -22,7 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 _ATTN_FLAGS = ["-fno-honor-nans", "-mno-amdgpu-ieee"]
 EXTRA_FLAGS = {"attention.hip": _ATTN_FLAGS, "attention_bwd.hip": _ATTN_FLAGS, "attention16.hip": _ATTN_FLAGS,
                "attention8.hip": _ATTN_FLAGS, "traj_clearance.hip": ["-Wall", "-Wextra"],
-               "traj_guide.hip": ["-Wall", "-Wextra"], "optim.hip": ["-Wall", "-Wextra"]}
+               "traj_guide.hip": ["-Wall", "-Wextra"], "traj_pins.hip": ["-Wall", "-Wextra"], "optim.hip": ["-Wall", "-Wextra"]}
 
 
 # development aid: extra hipcc flags for an A/B build on the GPU box, e.g. A3D_HIPCC_FLAGS="-DA3D_LIBM_SINCOS" python build.py --force
@@ -45,6 +45,7 @@ def build(force=False, verbose=False):
     hipcc = _hipcc()
     os.makedirs(OBJ_DIR, exist_ok=True)
     deps = [os.path.join(CSRC, "a3d_common.h"), os.path.join(CSRC, "attn_ring.h"), os.path.join(CSRC, "traj_points.h"),
+            os.path.join(CSRC, "pose_signal.h"),
             os.path.join(INCLUDE, "act3d_hip.h"),
             os.path.abspath(__file__)]
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]

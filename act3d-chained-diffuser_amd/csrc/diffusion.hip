@@ -14,6 +14,7 @@
 //   a3d_add_rows         seq + per-position embedding (seq1_sem_pos)            layers.py:104-105,132-133
 //   a3d_traj_update      cat(traj_xyz + delta, rot)                             diffusion_head.py:268-272
 #include "a3d_common.h"
+#include "pose_signal.h"
 #include "../../include/act3d_hip.h"
 
 namespace a3d {
@@ -190,32 +191,8 @@ __global__ void traj_update_kernel(const float* __restrict__ traj, const float* 
 // written from the closed forms: R(q) for a unit quaternion (w, x, y, z); 6D = the first two columns of R; back:
 // Gram-Schmidt of the two 3-vectors, then the quaternion from the best-conditioned of the four trace identities.
 // One thread per pose row; rows carry `extra` trailing channels that pass through.
-// pose_row_to_signal is the row map itself, shared with traj_condition_kernel so that both produce the same bits.
-__device__ __forceinline__ void pose_row_to_signal(const float* __restrict__ r, const float* __restrict__ bounds,
-                                                   float* __restrict__ o, int extra) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (bounds) {
-      const float lo = bounds[a], hi = bounds[3 + a];
-      o[a] = (r[a] - lo) / (hi - lo) * 2.0f - 1.0f;
-    } else {
-      o[a] = r[a];
-    }
-  }
-  float w = r[3], x = r[4], y = r[5], z = r[6];
-  const float nrm = fmaxf(sqrtf(w * w + x * x + y * y + z * z), 1e-10f);
-  w /= nrm; x /= nrm; y /= nrm; z /= nrm;
-  const float t = 2.0f / (w * w + x * x + y * y + z * z);
-  // first column of R, then the second
-  o[3] = 1.0f - t * (y * y + z * z);
-  o[4] = t * (x * y + z * w);
-  o[5] = t * (x * z - y * w);
-  o[6] = t * (x * y - z * w);
-  o[7] = 1.0f - t * (x * x + z * z);
-  o[8] = t * (y * z + x * w);
-  for (int e = 0; e < extra; ++e) o[9 + e] = r[7 + e];
-}
-
+// pose_row_to_signal is the row map itself (pose_signal.h), shared with traj_condition_kernel and traj_pins_kernel so that all
+// three produce the same bits.
 __global__ void pose_to_signal_kernel(const float* __restrict__ in, const float* __restrict__ bounds,
                                       float* __restrict__ out, int n, int extra) {
   const int Din = 7 + extra, Dout = 9 + extra;
@@ -229,7 +206,6 @@ __global__ void pose_to_signal_kernel(const float* __restrict__ in, const float*
 // trajectory.  One workgroup row per scene (blockIdx.x = b); its G trajectories b G + g are spread over blockIdx.y.  Every
 // workgroup converts the scene's two poses and counts its padding itself (a few hundred flops), so there is no second launch
 // and nothing is exchanged through memory.
-constexpr int TC_MAX_D = 32;                                      // signal channels a workgroup keeps in LDS (D = Dp + 2)
 __global__ __launch_bounds__(256) void traj_condition_kernel(
     const float* __restrict__ curr, int ldc, const float* __restrict__ goal, int ldg, const float* __restrict__ bounds,
     const unsigned char* __restrict__ tmask, const float* __restrict__ init_noise, float* __restrict__ cg,

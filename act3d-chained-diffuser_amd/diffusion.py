@@ -19,7 +19,8 @@ schedule (`scheduler="dpm++"` with `solver_order` / `lower_order_final`: the DPM
 `fused_conditioning=True` builds the sampler's conditioning tensors in one launch (a3d_traj_condition); `select` / `rot_weight`
 rank the candidates on the device and return the selected trajectory (rank_trajectories, a3d_traj_rank), optionally against the
 observed point cloud (trajectory_clearance, a3d_traj_clearance: the "clearance" term of a select rule); `guide` steers the waypoints
-off that cloud while they are drawn (guide_trajectories, a3d_traj_guide, between sampler steps).
+off that cloud while they are drawn (guide_trajectories, a3d_traj_guide, between sampler steps); `pins` keeps a committed prefix or
+via-points of the trajectory while the rest is sampled (traj_pins, a3d_traj_pins; prefix_pins for a receding-horizon replan).
 Training-mode dropout (p = 0.1 in every ParallelAttentionLayer --
 attention weights, residual branches, FFN -- and in the traj_encoder / regressor MLPs: layers.py:10,
 diffusion_head.py:46,183,193) runs on a device-resident Philox stream (csrc/dropout.hip, attention kernels): same
@@ -271,6 +272,132 @@ def traj_condition(curr_gripper, goal_gripper, bounds, trajectory_mask, init_noi
              None if noise is None else noise.data_ptr(), cg.data_ptr(), gg.data_ptr(), cond_data.data_ptr(), cond_mask.data_ptr(),
              kmask.data_ptr(), None if traj is None else traj.data_ptr(), B, G, Ln, Dp, 1 if use_goal else 0, O.L.stream())
     return cg, gg, cond_data, cond_mask, kmask, traj
+
+
+# ------------------------------------------------------------------------------------------------ pinned waypoints
+PINS_MAX = O.L.TRAJ_PINS_MAX               # pins per scene of one call (a3d_traj_pins keeps them in LDS)
+# channel groups of a pin -> the bit a3d_traj_pins reads: position = signal columns 0..2, rotation = 3..8, gripper = the extras 9..D-1
+PIN_CHANNELS = {"position": 1, "rotation": 2, "gripper": 4, "pose": 3, "all": 7}
+# pins as compute_trajectory(pins=...) takes them (a dict with these keys serves as well; channels may be left out = "pose")
+TrajectoryPins = collections.namedtuple("TrajectoryPins", ("poses", "index", "channels"), defaults=("pose",))
+# what a call with pins keeps on the planner: the rows asked for and which slots were written, (B, P) device tensors
+Pins = collections.namedtuple("Pins", ("index", "applied"))
+_PIN_INDEX_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+
+
+def pin_channel_bits(channels):
+    """"position" | "rotation" | "gripper" | "pose" (= position + rotation) | "all", or a tuple / list of them -> the bit mask"""
+    names = (channels,) if isinstance(channels, str) else channels
+    if not isinstance(names, (tuple, list)) or not names:
+        raise ValueError("pins: channels must be a name, a tuple of names from %s, or a (B, P) uint8 tensor of bit masks, got %r"
+                         % (sorted(PIN_CHANNELS), channels))
+    bits = 0
+    for n in names:
+        if not isinstance(n, str) or n not in PIN_CHANNELS:
+            raise ValueError("pins: unknown channel name %r (one of %s)" % (n, sorted(PIN_CHANNELS)))
+        bits |= PIN_CHANNELS[n]
+    return bits
+
+
+def check_pins(pins, B, Dp):
+    """Validates compute_trajectory's `pins` on the host (shapes, dtypes and Python values: nothing is launched or copied) and returns
+    (poses, index, channels): poses (B, P, Dp) floating point, index (B, P) integer -- the trajectory row of each pin, < 0 = unused
+    slot -- and channels as the bit mask of a3d_traj_pins, an int for every slot or a (B, P) uint8 tensor.  pins: a dict or a
+    namedtuple (TrajectoryPins) with "poses", "index" and optionally "channels": a name or a tuple of names from "position",
+    "rotation", "gripper" (the channels after the quaternion), "pose" (position + rotation, the default) and "all", or the (B, P)
+    uint8 tensor itself.  P <= 32; Dp must be the call's pose width.  Which rows are in range is decided on the device (the
+    padding is a device tensor): see traj_pins."""
+    if isinstance(pins, dict):
+        bad = [k for k in pins if k not in TrajectoryPins._fields]
+        if bad or "poses" not in pins or "index" not in pins:
+            raise ValueError("pins: a dict with the keys 'poses', 'index' and optionally 'channels', got %s" % sorted(pins))
+        poses, index, channels = pins["poses"], pins["index"], pins.get("channels", "pose")
+    elif isinstance(pins, tuple) and all(hasattr(pins, k) for k in TrajectoryPins._fields):
+        poses, index, channels = pins.poses, pins.index, pins.channels
+    else:
+        raise ValueError("pins must be a dict or a namedtuple with poses, index and channels, got %s" % type(pins).__name__)
+    if not torch.is_tensor(poses) or poses.dim() != 3 or not poses.is_floating_point():
+        raise ValueError("pins: poses must be a floating-point (B, P, Dp) tensor, got %s" % (
+            (tuple(poses.shape), poses.dtype) if torch.is_tensor(poses) else type(poses).__name__,))
+    P = poses.shape[1]
+    if poses.shape[0] != B or poses.shape[2] != Dp:
+        raise ValueError("pins: poses has shape %s, the call needs (B, P, Dp) = (%d, P, %d)" % (tuple(poses.shape), B, Dp))
+    if not 1 <= P <= PINS_MAX:
+        raise ValueError("pins: P = %d pins per scene, a call takes 1 to %d" % (P, PINS_MAX))
+    if not torch.is_tensor(index) or index.dtype not in _PIN_INDEX_DTYPES:
+        raise ValueError("pins: index must be an integer tensor, got %s" % (index.dtype if torch.is_tensor(index) else type(index).__name__,))
+    if tuple(index.shape) != (B, P):
+        raise ValueError("pins: index has shape %s, poses names (B, P) = %s" % (tuple(index.shape), (B, P)))
+    if torch.is_tensor(channels):
+        if channels.dtype != torch.uint8 or tuple(channels.shape) != (B, P):
+            raise ValueError("pins: a channels tensor holds one uint8 bit mask per slot, (B, P) = %s, got %s %s"
+                             % ((B, P), tuple(channels.shape), channels.dtype))
+    else:
+        channels = pin_channel_bits(channels)
+    return poses, index, channels
+
+
+def traj_pins(cond_data, cond_mask, traj, init_noise, pins, bounds, trajectory_mask, num_samples=1, use_goal=True):
+    """Pinned waypoints in ONE launch (a3d_traj_pins, csrc/traj_pins.hip): writes the pins of every scene into the conditioning
+    tensors of its G = num_samples trajectories, IN PLACE, and returns applied (B, P) uint8.  cond_data fp32 / cond_mask uint8:
+    (B G, L, D) contiguous, as traj_condition returns them; traj / init_noise: (B G, L, D) fp32 or None -- with both,
+    traj = init_noise + the pinned signal on the pinned elements (the start the other conditioned rows get); pins: check_pins;
+    trajectory_mask: (B, L) per scene, non-zero = padded.
+    With last = L - pad - 1, slot p of scene b is applied iff its channels are not empty and 1 <= index <= last - 1 (use_goal) or
+    1 <= index <= last: row 0, the goal row and padded rows are never touched, an out-of-range pin is dropped (applied = 0), never an
+    error -- the padding lives on the device and nothing is copied back.  The pose goes through pose_to_signal's row map (the same
+    bits); where two applied pins select one element the higher slot wins; elements no pin selects keep their bits."""
+    if trajectory_mask.dim() != 2:
+        raise ValueError("trajectory_mask must be (B, L), got %s" % (tuple(trajectory_mask.shape),))
+    B, Ln = trajectory_mask.shape
+    G = int(num_samples)
+    D = cond_data.shape[-1]
+    poses, index, channels = check_pins(pins, B, D - 2)
+    P = poses.shape[1]
+    for name, x, dt in (("cond_data", cond_data, torch.float32), ("cond_mask", cond_mask, torch.uint8), ("traj", traj, torch.float32)):
+        if x is not None and (tuple(x.shape) != (B * G, Ln, D) or x.dtype != dt or not x.is_contiguous()):
+            raise ValueError("%s is updated in place: it must be contiguous %s of shape %s, got %s %s" % (
+                name, dt, (B * G, Ln, D), tuple(x.shape), x.dtype))
+    if traj is not None and init_noise is None:
+        raise ValueError("traj needs init_noise (traj = init_noise + the pinned signal)")
+    if init_noise is not None and tuple(init_noise.shape) != (B * G, Ln, D):
+        raise ValueError("init_noise has shape %s, the call needs %s" % (tuple(init_noise.shape), (B * G, Ln, D)))
+    dev = cond_data.device
+    O.L.require_gpu(cond_data, cond_mask, traj, init_noise, bounds, trajectory_mask)
+    poses = poses.detach().to(device=dev, dtype=torch.float32)
+    if poses.stride(2) != 1 or poses.stride(1) < D - 2 or poses.stride(0) != P * poses.stride(1):
+        poses = poses.contiguous()
+    index = O._c(index.detach().to(device=dev, dtype=torch.int32))
+    channels = O._c(channels.to(dev)) if torch.is_tensor(channels) else torch.full((B, P), channels, device=dev, dtype=torch.uint8)
+    noise = None if (init_noise is None or traj is None) else O._c(init_noise.detach().float())
+    applied = torch.empty((B, P), device=dev, dtype=torch.uint8)
+    O.L.call("a3d_traj_pins", poses.data_ptr(), poses.stride(1), index.data_ptr(), channels.data_ptr(), O._c(bounds).data_ptr(),
+             _mask_bytes(trajectory_mask).data_ptr(), None if noise is None else noise.data_ptr(), cond_data.data_ptr(),
+             cond_mask.data_ptr(), None if traj is None else traj.data_ptr(), applied.data_ptr(), B, G, P, Ln, D - 2,
+             1 if use_goal else 0, O.L.stream())
+    return applied
+
+
+def prefix_pins(previous, executed, keep, channels="pose"):
+    """The pins of a receding-horizon replan: from the last plan `previous` (B, L, Dp) and the number of its steps `executed` since it
+    was made, pins that hold rows executed + 1 .. executed + keep of the old plan on rows 1 .. keep of the new one, so that the new
+    trajectory starts with what the robot is already committed to.  The caller passes the pose at row `executed` of the old plan
+    (where the robot is now) as curr_gripper: it becomes row 0.  Pure indexing on the device: a view of `previous` and an arange,
+    nothing is copied to the host.  Rows the new call cannot hold (its goal row, padding) are dropped there (last_pins.applied)."""
+    if not torch.is_tensor(previous) or previous.dim() != 3:
+        raise ValueError("previous must be a (B, L, Dp) trajectory, got %s" % (
+            tuple(previous.shape) if torch.is_tensor(previous) else type(previous).__name__,))
+    for name, v, lo in (("executed", executed, 0), ("keep", keep, 1)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+            raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))
+    if keep > PINS_MAX:
+        raise ValueError("keep = %d rows; a call takes at most %d pins per scene" % (keep, PINS_MAX))
+    B, Ln = previous.shape[:2]
+    if executed + keep > Ln - 1:
+        raise ValueError("previous has %d rows: rows %d .. %d do not all exist" % (Ln, executed + 1, executed + keep))
+    pin_channel_bits(channels)
+    index = torch.arange(1, keep + 1, device=previous.device, dtype=torch.int32)[None, :].expand(B, keep)
+    return TrajectoryPins(previous[:, executed + 1:executed + keep + 1], index, channels)
 
 
 # ------------------------------------------------------------------------------------------------ candidate ranking
@@ -1211,7 +1338,7 @@ _SamplingCall = collections.namedtuple("_SamplingCall", ("G", "K", "guide", "w_c
 
 def check_sampling_call(B, Ln, D, T, pcd_obs, have_goal=True, *, num_samples=None, num_inference_steps=None, scheduler="ddpm", eta=0.0,
                         init_noise=None, step_noise=None, n_steps=None, select=None, rot_weight=1.0, scene_mask=None,
-                        clear_margin=0.05, clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True):
+                        clear_margin=0.05, clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True, pins=None):
     """Every host-side check of a sampling call (compute_trajectory, Actioner.predict), on shapes and Python values alone: nothing
     is launched, so a bad argument raises before any kernel runs.  B scenes of Ln steps and D = pose width + 2 signal channels; T:
     the chain length, or None where the caller leaves the schedule and the noise tables to the sampler (Actioner.predict, whose
@@ -1239,6 +1366,8 @@ def check_sampling_call(B, Ln, D, T, pcd_obs, have_goal=True, *, num_samples=Non
                              % (step_noise.shape[0], K))
     if T is None:
         check_solver_args(scheduler, eta, solver_order, lower_order_final)
+    if pins is not None:
+        check_pins(pins, B, D - 2)
     guide = check_guide(guide)
     if guide is not None:
         check_guide_shape(G or 1, Ln, D)
@@ -1310,6 +1439,7 @@ class DiffusionPlanner(nn.Module):
         self._graph = None
         self.last_ranking = None
         self.last_guidance = None
+        self.last_pins = None
 
     # ---- helpers (diffusion_model.py:187-230)
     def tables(self, device):
@@ -1403,7 +1533,7 @@ class DiffusionPlanner(nn.Module):
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
                            return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None,
                            fused_conditioning=False, select=None, rot_weight=1.0, scene_mask=None, clear_margin=0.05,
-                           clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True):
+                           clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True, pins=None):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
@@ -1440,7 +1570,18 @@ class DiffusionPlanner(nn.Module):
         planner owns and refreshes); the margin, the skip and the point mask are clear_margin, clear_skip and scene_mask; the
         pinned rows are the in-painted ones.  It composes with num_samples / select unchanged.  self.last_guidance =
         Guidance(steps = the guided positions, nearest = the distances the LAST guide step found before its push, (B, G, L) or
-        (B, L)).  None (default): today's launches and today's bits."""
+        (B, L)).  None (default): today's launches and today's bits.
+        pins: pinned waypoints (check_pins: poses (B, P, Dp), index (B, P), channels; P <= 32), per scene.  The sampler in-paints
+        them exactly as it in-paints the start and the goal: one more launch (traj_pins, a3d_traj_pins) fills the in-painting data /
+        mask and the noisy start trajectory of every candidate of the scene, on either conditioning path with the same bits, and
+        every step of every sampler path and scheduler then returns the pinned elements unchanged.  A pin is applied iff its row lies
+        strictly between row 0 and the goal row (up to the last valid row without a goal) -- start and goal keep priority, padded
+        rows are never touched; out-of-range pins are dropped on the device and self.last_pins = Pins(index, applied) (device
+        tensors, nothing is synchronised) reports them.  prefix_pins builds the pins of a receding-horizon replan.  With use_graph
+        the launch stays outside the captured loop, whose in-painting tensors and start trajectory every replay refreshes: other
+        pins, another P or none replay the same graph.  With guide, a row whose POSITION is pinned is never pushed (the guide reads
+        the first mask byte of a row); a rotation-only pin leaves the row free.  None (default): today's launches and today's bits,
+        last_pins = None."""
         head = self.prediction_head
         dev = pcd_obs.device
         B_scene, Ln = trajectory_mask.shape
@@ -1450,7 +1591,7 @@ class DiffusionPlanner(nn.Module):
                                    num_inference_steps=num_inference_steps, scheduler=scheduler, eta=eta, init_noise=init_noise,
                                    step_noise=step_noise, n_steps=n_steps, select=select, rot_weight=rot_weight, scene_mask=scene_mask,
                                    clear_margin=clear_margin, clear_skip=clear_skip, guide=guide, solver_order=solver_order,
-                                   lower_order_final=lower_order_final)
+                                   lower_order_final=lower_order_final, pins=pins)
         # ---- the plan: which launches serve the call, from the shapes and the CU count alone
         multi = head.attn_rounds * head.feat_scales > 1
         plan = sampler_plan(B_scene, call.G, Ln, D, head.curr_gripper_embed.weight.shape[1], head.num_attn_heads, self.n_steps,
@@ -1459,7 +1600,7 @@ class DiffusionPlanner(nn.Module):
         tb = self.tables(dev)
         sched = self.schedule(dev, plan.K, scheduler, eta, solver_order, lower_order_final) if plan.scheduled else None
         c = self._condition(plan, sched, call.G, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper,
-                            init_noise, step_noise, visual_tokens, fused_conditioning)
+                            init_noise, step_noise, visual_tokens, fused_conditioning, pins)
         replay = use_graph and not return_trace
         state, static, key, gd = self._sampler_state(plan, sched, call, c, pcd_obs, trajectory_mask, scene_mask, fused_conditioning,
                                                      replay)
@@ -1474,10 +1615,13 @@ class DiffusionPlanner(nn.Module):
                             scene_mask, clear_margin, clear_skip)
 
     def _condition(self, plan, sched, G, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, init_noise,
-                   step_noise, visual_tokens, fused_conditioning):
+                   step_noise, visual_tokens, fused_conditioning, pins=None):
         """The conditioning of a sampling call -> _Conditioned: visual tokens, the two poses as signals, the in-painting data / mask,
-        the key mask, the candidate reshaping / expansion, the noise defaults and the noisy start trajectory."""
+        the key mask, the candidate reshaping / expansion, the noise defaults and the noisy start trajectory.  pins: one more launch
+        (traj_pins) on the per-trajectory in-painting tensors, with the call's own per-scene mask; self.last_pins keeps its record."""
         dev = pcd_obs.device
+        scene_mask_rows = trajectory_mask                   # per scene, whatever the candidate expansion below does
+        self.last_pins = None
         B_scene, Ln = trajectory_mask.shape
         D = curr_gripper.shape[-1] + 2
         B = B_scene * (G or 1)
@@ -1492,6 +1636,8 @@ class DiffusionPlanner(nn.Module):
                 init_noise = init_noise.to(dev).float().reshape(B, Ln, -1)
             cg, gg, cond_data, cond_mask_u8, kmask, traj = traj_condition(
                 curr_gripper, goal_gripper, self.gripper_loc_bounds, trajectory_mask, init_noise, G or 1, self._use_goal_at_test)
+            if pins is not None:
+                self._pin(pins, cond_data, cond_mask_u8, traj, init_noise, scene_mask_rows, G or 1)
         if G is not None:
             if init_noise is not None:
                 init_noise = init_noise.reshape(B, Ln, -1)
@@ -1521,6 +1667,9 @@ class DiffusionPlanner(nn.Module):
             if plan.group:
                 # per trajectory from here on: conditioning, masks, noise, the trajectory itself (scene-major); ctx / instr stay per scene
                 cond_mask_u8, cond_data, kmask = (x.repeat_interleave(G, 0).contiguous() for x in (cond_mask_u8, cond_data, kmask))
+            if pins is not None:
+                # on the per-trajectory tensors, before the start trajectory is formed from them: the kernel expands the scene's pins
+                self._pin(pins, cond_data, cond_mask_u8, None, None, scene_mask_rows, G or 1)
         if init_noise is None:
             init_noise = torch.randn((B, Ln, D), device=dev)
         if sched is not None and sched.noise_free:
@@ -1533,6 +1682,13 @@ class DiffusionPlanner(nn.Module):
             traj = (init_noise.to(dev).float() + cond_data).contiguous()
         return _Conditioned(B_scene, B, tokens, ctx_xyz, instruction, cg, gg, trajectory_mask, cond_data, cond_mask_u8, kmask,
                             step_noise, traj)
+
+    def _pin(self, pins, cond_data, cond_mask_u8, traj, init_noise, trajectory_mask, G):
+        """traj_pins on the call's in-painting tensors; last_pins = Pins(index, applied), (B, P) device tensors, nothing synchronised"""
+        applied = traj_pins(cond_data, cond_mask_u8, traj, init_noise, pins, self.gripper_loc_bounds, trajectory_mask, G,
+                            self._use_goal_at_test)
+        index = pins["index"] if isinstance(pins, dict) else pins.index
+        self.last_pins = Pins(index.detach().to(device=applied.device, dtype=torch.int32), applied)
 
     def _sampler_state(self, plan, sched, call, c, pcd_obs, trajectory_mask, scene_mask, fused_conditioning, replay):
         """The step-invariant state of the planned path -> (state, static, key, gd): static is what a captured graph refreshes in

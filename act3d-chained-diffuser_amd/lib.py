@@ -133,6 +133,9 @@ ADAMW_CLIP_WS_DOUBLES = _DEFINES["A3D_ADAMW_CLIP_WS_DOUBLES"]
 # a3d_adamw_sched_step's decay_kind: {"constant": A3D_LR_CONSTANT, "linear": .., "cosine": ..}
 LR_DECAY_KINDS = {k[len("A3D_LR_"):].lower(): v for k, v in _DEFINES.items() if k.startswith("A3D_LR_")}
 
+# pins per scene of one a3d_traj_pins call
+TRAJ_PINS_MAX = _DEFINES["A3D_TRAJ_PINS_MAX"]
+
 _lib = None
 
 

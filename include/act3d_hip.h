@@ -523,6 +523,25 @@ int a3d_signal_to_pose(const float* signal, const float* bounds, float* out, int
 int a3d_traj_condition(const float* curr, int ldc, const float* goal, int ldg, const float* bounds, const unsigned char* tmask,
                        const float* init_noise, float* cg, float* gg, float* cond_data, unsigned char* cond_mask,
                        unsigned char* kmask, float* traj, int B, int G, int L, int Dp, int use_goal, void* stream);
+/* Pinned waypoints: more poses for the in-painting seam of diffusion_model.py:131-168, in one launch after the conditioning tensors
+ * of the call exist (a3d_traj_condition or the op-by-op block; csrc/traj_pins.hip).  None in the reference, which pins the start and
+ * the goal only.  poses: [B][P] pose rows [xyz | quat (w, x, y, z) | extra..] of Dp >= 7 channels, row stride ldp >= Dp floats;
+ * index: [B][P] the trajectory row of each pin, < 0 = unused slot; channels: [B][P] bytes, bit 0 = position (signal columns 0..2),
+ * bit 1 = rotation (3..8), bit 2 = extras (9..D-1), higher bits ignored; bounds: device [2][3]; tmask: [B][L] bytes, non-zero = padded
+ * step.  D = Dp + 2 <= 32, 1 <= P <= A3D_TRAJ_PINS_MAX.  With last = L - pad - 1 (pad = non-zero entries of the scene's mask row),
+ * slot p of scene b is APPLIED iff its channel bits are not all zero and 1 <= index <= last - 1 (use_goal) or 1 <= index <= last
+ * (no goal): row 0, the goal row, padded rows and all-padding scenes are never touched, the start and the goal keep priority.  An
+ * out-of-range pin is dropped, not an error (no host synchronisation); applied [B][P] bytes reports 1 / 0 per slot.  The pose is
+ * converted by the row map of a3d_pose_to_signal (the same bits).  For every applied slot, every selected channel c and every
+ * candidate g of the scene (trajectory b G + g):
+ *   cond_data [B G][L][D] = sig[c];  cond_mask [B G][L][D] = 1;  traj [B G][L][D] = init_noise + sig[c] (one fp32 add) when traj is
+ *   given (traj needs init_noise; both may be NULL).
+ * Where two applied slots select the same element the HIGHER slot wins; an element no applied pin selects is not written.
+ * Deterministic: every thread scans the P slots for its own element, no atomics.  Stream-ordered, capturable. */
+#define A3D_TRAJ_PINS_MAX 32
+int a3d_traj_pins(const float* poses, int ldp, const int* index, const unsigned char* channels, const float* bounds,
+                  const unsigned char* tmask, const float* init_noise, float* cond_data, unsigned char* cond_mask, float* traj,
+                  unsigned char* applied, int B, int G, int P, int L, int Dp, int use_goal, void* stream);
 /* Ranks the G <= 64 sampled candidates of every scene and selects one, in one launch (one workgroup per scene; csrc/traj_rank.hip).
  * None in the reference: Actioner.predict (online_evaluation/utils_with_rlbench.py:120-230) consumes one trajectory per scene;
  * the distances follow TrajectoryCriterion.compute_metrics (main_trajectory.py:303-343: position L2 per step, sign-invariant
