@@ -44,7 +44,8 @@ def build(force=False, verbose=False):
     """Compile every csrc/*.hip for gfx950 and link libact3d_hip.so.  Returns the library path."""
     hipcc = _hipcc()
     os.makedirs(OBJ_DIR, exist_ok=True)
-    deps = [os.path.join(CSRC, "a3d_common.h"), os.path.join(CSRC, "attn_ring.h"), os.path.join(CSRC, "traj_points.h"),
+    deps = [os.path.join(CSRC, "a3d_common.h"), os.path.join(CSRC, "attn_ring.h"), os.path.join(CSRC, "attn_launch.h"),
+            os.path.join(CSRC, "traj_points.h"),
             os.path.join(CSRC, "pose_signal.h"),
             os.path.join(INCLUDE, "act3d_hip.h"),
             os.path.abspath(__file__)]

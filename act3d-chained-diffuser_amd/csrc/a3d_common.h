@@ -229,6 +229,17 @@ __device__ __forceinline__ uint32_t drop_keep8(DropKey k, uint32_t c0, uint32_t 
   return bits;
 }
 
+// host: threshold and keep-scale of a dropout probability; p outside [0, 1) (NaN included) is refused under the entry's name
+static inline int drop_params(const char* fn, float p, uint32_t* thr16, float* scale) {
+  if (!(p >= 0.f) || !(p < 1.f)) {
+    set_error("%s: dropout probability %g outside [0, 1)", fn, (double)p);
+    return A3D_ERR_ARG;
+  }
+  *thr16 = (uint32_t)lrintf(p * 65536.0f);
+  *scale = 1.0f / (1.0f - p);
+  return A3D_OK;
+}
+
 // XCD-aware workgroup decoding (MI355X: 8 XCDs with private 4 MiB L2s; workgroup i is dispatched to XCD i % 8).
 // All `per_group` workgroups that share one (sample, head)'s K/V or Q/dO tensors are placed on ONE XCD, so that
 // those tensors are fetched from HBM once and re-read from that XCD's L2.  Grid = xcd_grid(ngroups, per_group).

@@ -16,9 +16,8 @@
 //   PV = V_hi P_hi + V_hi P_lo + V_lo P_hi (3 MFMAs per 32 keys).
 // Backward: attention_bwd.hip (split-bf16 MFMA on the same operand formats; the exact-f32 MFMA backward that preceded it was
 //   deleted in round 4 -- one A/B reference per kernel).
-#include "a3d_common.h"
+#include "attn_launch.h"
 #include "../../include/act3d_hip.h"
-#include <stdlib.h>
 
 namespace a3d {
 
@@ -304,59 +303,31 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(
 
 using namespace a3d;
 
-static int check_attn_args(const char* fn, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit) {
-  if (B <= 0 || H <= 0 || Lq <= 0 || Lqp < Lq || (Lqp % 16) != 0 || S <= 0 || Sp < S || (Sp % KC) != 0 ||
-      nsplit < 1 || nsplit > 64) {
-    set_error("%s: bad argument (B=%d H=%d Lq=%d Lqp=%d S=%d Sp=%d nsplit=%d)", fn, B, H, Lq, Lqp, S, Sp, nsplit);
-    return A3D_ERR_ARG;
-  }
-  return A3D_OK;
-}
-
-static int attn_fwd_launch(const void* Qs, const void* Ks, const void* Vt, const unsigned char* kmask,
-                           float* O, float* LSE, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp,
-                           int nsplit, const unsigned long long* drop_state, unsigned int drop_site, float drop_p,
+static int attn_fwd_launch(const char* fn, const void* Qs, const void* Ks, const void* Vt, const unsigned char* kmask, float* O,
+                           float* LSE, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit,
+                           const unsigned long long* drop_state, unsigned int drop_site, float drop_p, bool drop_required,
                            void* stream) {
-  int rc = check_attn_args("a3d_attn_fwd", B, H, Lq, Lqp, S, Sp, nsplit);
+  int rc = attn_check_shapes(fn, B, H, Lq, Lqp, S, Sp, nsplit, 16, 0);
   if (rc) return rc;
-  if (!Qs || !Ks || !Vt || !O || !LSE || (nsplit > 1 && !ws)) {
-    set_error("a3d_attn_fwd: null pointer");
-    return A3D_ERR_ARG;
-  }
-  const bool drop = drop_state != nullptr && drop_p > 0.f;
-  if (drop_state && !(drop_p >= 0.f && drop_p < 1.f)) {
-    set_error("a3d_attn_fwd_dropout: dropout probability %g outside [0, 1)", (double)drop_p);
-    return A3D_ERR_ARG;
-  }
-  const unsigned int thr = drop ? (unsigned int)lrintf(drop_p * 65536.0f) : 0u;
-  const float dscale = drop ? 1.0f / (1.0f - drop_p) : 1.0f;
+  AttnDrop d;
+  rc = attn_drop_decode(fn, drop_state, drop_site, drop_p, drop_required, &d);
+  if (rc) return rc;
+  if (!Qs || !Ks || !Vt || !O || !LSE || (nsplit > 1 && !ws)) { set_error("%s: null pointer", fn); return A3D_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
-  const size_t rows = (size_t)B * H * Lqp;
-  float* Op = ws;
-  float* Mp = ws ? ws + (size_t)nsplit * rows * HDP : nullptr;
-  float* Lp = ws ? Mp + (size_t)nsplit * rows : nullptr;
-  // two query tiles per wave (128 queries per workgroup) once the query set fills them; A3D_ATTN_QT=1 forces the narrow form
-  static const int qt_env = getenv("A3D_ATTN_QT") ? atoi(getenv("A3D_ATTN_QT")) : 0;
-  const int QT = qt_env ? qt_env : (Lq > 64 ? 2 : 1);
-  dim3 grid(xcd_grid(B * H, cdiv(Lqp, 64 * QT) * nsplit));
-  const unsigned long long* nostate = nullptr;
-#define A3D_LAUNCH_FWD(DROPV, QTV, ST, SITE, THR, SC)                                                                    \
-  hipLaunchKernelGGL((attn_fwd_kernel<DROPV, QTV>), grid, dim3(256), 0, s, (const unsigned short*)Qs,                   \
-                     (const unsigned short*)Ks, (const unsigned short*)Vt, kmask, O, LSE, Op, Mp, Lp, B, H, Lq, Lqp, S, \
-                     Sp, nsplit, ST, SITE, THR, SC)
-  if (drop) {
-    if (QT == 2) A3D_LAUNCH_FWD(true, 2, drop_state, drop_site, thr, dscale);
-    else A3D_LAUNCH_FWD(true, 1, drop_state, drop_site, thr, dscale);
-  } else {
-    if (QT == 2) A3D_LAUNCH_FWD(false, 2, nostate, 0u, 0u, 1.0f);
-    else A3D_LAUNCH_FWD(false, 1, nostate, 0u, 0u, 1.0f);
-  }
-#undef A3D_LAUNCH_FWD
+  const AttnWs w = attn_ws_carve(ws, B, H, Lqp, nsplit);
+  const AttnTiles t = attn_tiles(B, H, Lq, Lqp, Sp, nsplit);
+  with_bool(d.state != nullptr, [&](auto drop) {
+    with_int<2, 1>(t.QT, [&](auto qt) {
+      hipLaunchKernelGGL((attn_fwd_kernel<decltype(drop)::value, decltype(qt)::value>), t.gq, dim3(256), 0, s,
+                         (const unsigned short*)Qs, (const unsigned short*)Ks, (const unsigned short*)Vt, kmask, O, LSE, w.Op, w.Mp,
+                         w.Lp, B, H, Lq, Lqp, S, Sp, nsplit, d.state, d.site, d.thr, d.scale);
+    });
+  });
   rc = check_launch("a3d_attn_fwd");
   if (rc) return rc;
   if (nsplit > 1) {
-    const int cg = (int)std::min<size_t>((rows * HDP + 255) / 256, 4096);
-    hipLaunchKernelGGL(attn_combine_kernel, dim3(cg), dim3(256), 0, s, Op, Mp, Lp, O, LSE, B, H, Lq, Lqp, nsplit);
+    const int cg = (int)std::min<size_t>(((size_t)B * H * Lqp * HDP + 255) / 256, 4096);
+    hipLaunchKernelGGL(attn_combine_kernel, dim3(cg), dim3(256), 0, s, w.Op, w.Mp, w.Lp, O, LSE, B, H, Lq, Lqp, nsplit);
     rc = check_launch("a3d_attn_fwd(combine)");
   }
   return rc;
@@ -365,18 +336,17 @@ static int attn_fwd_launch(const void* Qs, const void* Ks, const void* Vt, const
 extern "C" int a3d_attn_fwd(const void* Qs, const void* Ks, const void* Vt, const unsigned char* kmask,
                             float* O, float* LSE, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp,
                             int nsplit, void* stream) {
-  return attn_fwd_launch(Qs, Ks, Vt, kmask, O, LSE, ws, B, H, Lq, Lqp, S, Sp, nsplit, nullptr, 0u, 0.f, stream);
+  return attn_fwd_launch("a3d_attn_fwd", Qs, Ks, Vt, kmask, O, LSE, ws, B, H, Lq, Lqp, S, Sp, nsplit, nullptr, 0u, 0.f, false, stream);
 }
 
 extern "C" int a3d_attn_fwd_dropout(const void* Qs, const void* Ks, const void* Vt, const unsigned char* kmask,
                                     float* O, float* LSE, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp,
                                     int nsplit, const unsigned long long* drop_state, unsigned int drop_site,
                                     float drop_p, void* stream) {
-  if (!drop_state) { set_error("a3d_attn_fwd_dropout: null dropout state"); return A3D_ERR_ARG; }
-  return attn_fwd_launch(Qs, Ks, Vt, kmask, O, LSE, ws, B, H, Lq, Lqp, S, Sp, nsplit, drop_state, drop_site, drop_p, stream);
+  return attn_fwd_launch("a3d_attn_fwd_dropout", Qs, Ks, Vt, kmask, O, LSE, ws, B, H, Lq, Lqp, S, Sp, nsplit, drop_state, drop_site,
+                         drop_p, true, stream);
 }
 
 extern "C" size_t a3d_attn_fwd_ws_floats(int B, int H, int Lqp, int nsplit) {
-  if (nsplit <= 1) return 0;
-  return (size_t)nsplit * B * H * Lqp * (HDP + 2);
+  return nsplit <= 1 ? 0 : attn_ws_plan(B, H, Lqp, nsplit).floats;
 }

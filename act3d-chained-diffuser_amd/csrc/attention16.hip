@@ -47,9 +47,14 @@
 //            fragment); the value planes carry 1.0 in the padded channel 15 of the hi plane (softmax denominator)
 //   dOr      [B][H][Lqp][32] fp16 : hi | lo of the row-normalised dO * ln 2;  pack: see PK_* below
 // Scores live in log2 units (q carries log2 e): LSE2 = log2 sum_k 2^s2.
+//
+// Launch code (end of the file, on the host-side plan of attn_launch.h).  What selects a kernel variant, and nothing else does:
+//   QT = 2 when Lq > 64 (forward, dQ), KT = 2 when B H (Sp / 128) >= 1024 and Lq > 16 (dK / dV) -- from the shapes alone;
+//   PP = 3 when a backward follows, 2 for nograd passes; VR by entry (a3d_attn16_fwd_rows / a3d_attn16_fwd); DROP when a dropout
+//   state with p > 0 is passed; A3D_ATTN_FAST=1 puts PP = 1 and GP = 1 in place of PP = 2 | 3 and GP = 2.
 #include "attn_ring.h"
+#include "attn_launch.h"
 #include "../../include/act3d_hip.h"
-#include <stdlib.h>
 
 namespace a3d {
 
@@ -72,7 +77,6 @@ namespace a3d {
 // there are, and what the round-3 measurement attributed the 1.27e-3 model-level error to are the one or two keys per query that
 // carry most of the weight on the gain-3 fixtures -- those keep both parts.  PP = 3: both parts everywhere (the round-5 kernel).
 constexpr float LO_SPAN = 6.0f;
-constexpr int A3D_ATTN16_V_ROWS = 1, A3D_ATTN16_NOGRAD = 2;
 constexpr int FWD_NB = 4;
 // VR: the values arrive as ROWS ([B][H][Sp][32], channel 15 of the hi part = 1.0) and the V^T fragments come from transposed LDS reads
 // (attn_ring.h tr_frag) -- the rows-only operand set of round 6: the projection kernel writes ONE layout of K and V; !VR: value planes.
@@ -1028,95 +1032,54 @@ __global__ __launch_bounds__(256, 2) void attn16_bwd_dkv_kernel(
 
 using namespace a3d;
 
-int a3d::attn16_check_shapes(const char* fn, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit, int qmod) {
-  if (B <= 0 || H <= 0 || Lq <= 0 || Lqp < Lq || (Lqp % qmod) != 0 || S <= 0 || Sp < S || (Sp % C16) != 0 || nsplit < 1 ||
-      nsplit > 64 || Sp > MASKW * 32) {
-    set_error("%s: bad argument (B=%d H=%d Lq=%d Lqp=%d S=%d Sp=%d nsplit=%d; need Lqp %% %d == 0, Sp %% 64 == 0, Sp <= %d)", fn,
-              B, H, Lq, Lqp, S, Sp, nsplit, qmod, MASKW * 32);
-    return A3D_ERR_ARG;
-  }
-  return A3D_OK;
-}
-
-static int drop_params(const char* fn, const unsigned long long* drop_state, float drop_p, bool& drop, unsigned int& thr,
-                       float& dscale) {
-  drop = drop_state != nullptr && drop_p > 0.f;
-  if (drop_state && !(drop_p >= 0.f && drop_p < 1.f)) {
-    set_error("%s: dropout probability %g outside [0, 1)", fn, (double)drop_p);
-    return A3D_ERR_ARG;
-  }
-  thr = drop ? (unsigned int)lrintf(drop_p * 65536.0f) : 0u;
-  dscale = drop ? 1.0f / (1.0f - drop_p) : 1.0f;
-  return A3D_OK;
-}
-
-// flags: A3D_ATTN16_V_ROWS -- Vp holds value ROWS (ones in channel 15 of the hi part; a3d_proj_rope_split16 parts | 8);
-//        A3D_ATTN16_NOGRAD -- no backward will follow: the low part of P is formed only where a key dominates (PP = 2, see the kernel)
+// ------------------------------------------------------------------------------------------------ launch code (plan: attn_launch.h)
+// v_rows: Vp holds value ROWS (ones in channel 15 of the hi part; a3d_proj_rope_split16 parts | 8), else value planes.
+// nograd: no backward will follow.  P parts (PP): both everywhere (3) when a backward follows -- its D = dO . O and its recomputed
+// weights must agree with this pass to ~2^-20: near-uniform attention has gradients that are a small covariance on a large common mode
+// (measured in round 6: the adaptive low part leaves the forward inside 5e-4 but puts the level-0 ghost-attention gradients of the
+// cfg-4 shape 1-3 % off); adaptive (2) for gradient-free passes (evaluation, sampling); A3D_ATTN_FAST=1: the single-part kernels (1).
 static int attn16_fwd_launch(const char* fn, const void* Qr, const void* Kr, const void* Vp, const unsigned char* kmask, float* O,
                              float* LSE2, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit,
-                             const unsigned long long* drop_state, unsigned int drop_site, float drop_p, int flags, void* stream);
+                             const unsigned long long* drop_state, unsigned int drop_site, float drop_p, bool v_rows, bool nograd,
+                             void* stream) {
+  int rc = attn_check_shapes(fn, B, H, Lq, Lqp, S, Sp, nsplit, 16, MASKW * 32);
+  if (rc) return rc;
+  AttnDrop d;
+  rc = attn_drop_decode(fn, drop_state, drop_site, drop_p, false, &d);
+  if (rc) return rc;
+  if (!Qr || !Kr || !Vp || !O || !LSE2 || (nsplit > 1 && !ws)) { set_error("%s: null pointer", fn); return A3D_ERR_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  const AttnWs w = attn_ws_carve(ws, B, H, Lqp, nsplit);
+  const AttnTiles t = attn_tiles(B, H, Lq, Lqp, Sp, nsplit);
+  with_bool(d.state != nullptr, [&](auto drop) {
+    with_int<2, 1>(t.QT, [&](auto qt) {
+      with_int<1, 2, 3>(attn_fast() ? 1 : nograd ? 2 : 3, [&](auto pp) {
+        with_bool(v_rows, [&](auto vr) {
+          hipLaunchKernelGGL((attn16_fwd_kernel<decltype(drop)::value, decltype(qt)::value, decltype(pp)::value, decltype(vr)::value>),
+                             t.gq, dim3(256), 0, s, (const unsigned short*)Qr, (const unsigned short*)Kr, (const unsigned short*)Vp,
+                             kmask, O, LSE2, w.Op, w.Mp, w.Lp, B, H, Lq, Lqp, S, Sp, nsplit, d.state, d.site, d.thr, d.scale);
+        });
+      });
+    });
+  });
+  rc = check_launch(fn);
+  if (rc) return rc;
+  if (nsplit > 1) rc = attn16_launch_combine(w.Op, w.Mp, w.Lp, O, LSE2, B, H, Lq, Lqp, nsplit, s);
+  return rc;
+}
+
 extern "C" int a3d_attn16_fwd(const void* Qr, const void* Kr, const void* Vp, const unsigned char* kmask, float* O,
                               float* LSE2, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit,
                               const unsigned long long* drop_state, unsigned int drop_site, float drop_p, void* stream) {
   return attn16_fwd_launch("a3d_attn16_fwd", Qr, Kr, Vp, kmask, O, LSE2, ws, B, H, Lq, Lqp, S, Sp, nsplit, drop_state, drop_site,
-                           drop_p, 0, stream);
+                           drop_p, false, false, stream);
 }
 extern "C" int a3d_attn16_fwd_rows(const void* Qr, const void* Kr, const void* Vr, const unsigned char* kmask, float* O,
                                    float* LSE2, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit,
                                    const unsigned long long* drop_state, unsigned int drop_site, float drop_p, int nograd,
                                    void* stream) {
   return attn16_fwd_launch("a3d_attn16_fwd_rows", Qr, Kr, Vr, kmask, O, LSE2, ws, B, H, Lq, Lqp, S, Sp, nsplit, drop_state,
-                           drop_site, drop_p, A3D_ATTN16_V_ROWS | (nograd ? A3D_ATTN16_NOGRAD : 0), stream);
-}
-static int attn16_fwd_launch(const char* fn, const void* Qr, const void* Kr, const void* Vp, const unsigned char* kmask, float* O,
-                             float* LSE2, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit,
-                             const unsigned long long* drop_state, unsigned int drop_site, float drop_p, int flags, void* stream) {
-  const bool v_rows = (flags & A3D_ATTN16_V_ROWS) != 0, nograd = (flags & A3D_ATTN16_NOGRAD) != 0;
-  int rc = attn16_check_shapes(fn, B, H, Lq, Lqp, S, Sp, nsplit, 16);
-  if (rc) return rc;
-  if (!Qr || !Kr || !Vp || !O || !LSE2 || (nsplit > 1 && !ws)) { set_error("%s: null pointer", fn); return A3D_ERR_ARG; }
-  bool drop; unsigned int thr; float dscale;
-  rc = drop_params(fn, drop_state, drop_p, drop, thr, dscale);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t rows = (size_t)B * H * Lqp;
-  float* Op = ws;
-  float* Mp = ws ? ws + (size_t)nsplit * rows * HDP : nullptr;
-  float* Lp = ws ? Mp + (size_t)nsplit * rows : nullptr;
-  static const int qt_env = getenv("A3D_ATTN_QT") ? atoi(getenv("A3D_ATTN_QT")) : 0;
-  const int QT = qt_env ? qt_env : (Lq > 64 ? 2 : 1);
-  dim3 grid(xcd_grid(B * H, cdiv(Lqp, 64 * QT) * nsplit));
-  const unsigned long long* nostate = nullptr;
-  static const bool fast = getenv("A3D_ATTN_FAST") && atoi(getenv("A3D_ATTN_FAST")) != 0;     // single-fp16 P in the forward
-#define A3D_L16F(DROPV, QTV, PPV, ST, SITE, THR, SC)                                                                     \
-  do { if (v_rows) hipLaunchKernelGGL((attn16_fwd_kernel<DROPV, QTV, PPV, true>), grid, dim3(256), 0, s, (const unsigned short*)Qr, \
-                     (const unsigned short*)Kr, (const unsigned short*)Vp, kmask, O, LSE2, Op, Mp, Lp, B, H, Lq, Lqp, S, \
-                     Sp, nsplit, ST, SITE, THR, SC);                                                                     \
-       else hipLaunchKernelGGL((attn16_fwd_kernel<DROPV, QTV, PPV, false>), grid, dim3(256), 0, s, (const unsigned short*)Qr, \
-                     (const unsigned short*)Kr, (const unsigned short*)Vp, kmask, O, LSE2, Op, Mp, Lp, B, H, Lq, Lqp, S, \
-                     Sp, nsplit, ST, SITE, THR, SC); } while (0)
-  // P parts: both everywhere when a backward follows (its D = dO . O and its recomputed weights must agree with this pass to ~2^-20:
-  // near-uniform attention has gradients that are a small covariance on a large common mode -- measured in round 6: the adaptive low
-  // part leaves the forward inside 5e-4 but puts the level-0 ghost-attention gradients of the cfg-4 shape 1-3 % off); adaptive for
-  // gradient-free passes (evaluation, sampling); A3D_ATTN_LO_ADAPT=1 forces adaptive, A3D_ATTN_FAST=1 the single-part kernels
-  static const bool lo_adapt_env = getenv("A3D_ATTN_LO_ADAPT") && atoi(getenv("A3D_ATTN_LO_ADAPT")) != 0;
-  const bool lo_adapt = nograd || lo_adapt_env;
-#define A3D_L16F_PP(DROPV, QTV, ST, SITE, THR, SC)                                                                       \
-  do { if (fast) A3D_L16F(DROPV, QTV, 1, ST, SITE, THR, SC); else if (lo_adapt) A3D_L16F(DROPV, QTV, 2, ST, SITE, THR, SC);   \
-       else A3D_L16F(DROPV, QTV, 3, ST, SITE, THR, SC); } while (0)
-  if (drop) {
-    if (QT == 2) A3D_L16F_PP(true, 2, drop_state, drop_site, thr, dscale);
-    else A3D_L16F_PP(true, 1, drop_state, drop_site, thr, dscale);
-  } else {
-    if (QT == 2) A3D_L16F_PP(false, 2, nostate, 0u, 0u, 1.0f);
-    else A3D_L16F_PP(false, 1, nostate, 0u, 0u, 1.0f);
-  }
-#undef A3D_L16F_PP
-#undef A3D_L16F
-  rc = check_launch(fn);
-  if (rc) return rc;
-  if (nsplit > 1) rc = attn16_launch_combine(Op, Mp, Lp, O, LSE2, B, H, Lq, Lqp, nsplit, s);
-  return rc;
+                           drop_site, drop_p, true, nograd != 0, stream);
 }
 
 int a3d::attn16_launch_combine(const float* Op, const float* Mp, const float* Lp, float* O, float* LSE2, int B, int H, int Lq,
@@ -1136,16 +1099,16 @@ extern "C" int a3d_attn16_bwd(const void* Qr, const void* Qp, const void* Kr, co
                               void* pack, float* D, int* rexp, float* dQp, float* dK, float* dV, int B, int H, int Lq,
                               int Lqp, int S, int Sp, int nsplit, const unsigned long long* drop_state,
                               unsigned int drop_site, float drop_p, void* stream) {
-  int rc = attn16_check_shapes("a3d_attn16_bwd", B, H, Lq, Lqp, S, Sp, nsplit, 64);
+  int rc = attn_check_shapes("a3d_attn16_bwd", B, H, Lq, Lqp, S, Sp, nsplit, 64, MASKW * 32);
+  if (rc) return rc;
+  AttnDrop d;
+  rc = attn_drop_decode("a3d_attn16_bwd", drop_state, drop_site, drop_p, false, &d);
   if (rc) return rc;
   (void)Qp; (void)Kp;      // round 6: the q / k planes are no longer read (K^T comes from transposed LDS reads of the rows); may be NULL
   if (!Qr || !Kr || !Vr || !O || !dO || !LSE2 || !dOr || !pack || !D || !rexp || !dQp || !dK || !dV) {
     set_error("a3d_attn16_bwd: null pointer");
     return A3D_ERR_ARG;
   }
-  bool drop; unsigned int thr; float dscale;
-  rc = drop_params("a3d_attn16_bwd", drop_state, drop_p, drop, thr, dscale);
-  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)Lqp * 12 + (size_t)2 * PREP_GROUP * 64 * 64;
   constexpr size_t PREP_LDS_MAX = 150 * 1024;          // the dynamic-LDS attribute set below (160 KB per CU on gfx950)
@@ -1164,43 +1127,28 @@ extern "C" int a3d_attn16_bwd(const void* Qr, const void* Qp, const void* Kr, co
                      (unsigned short*)dOr, D, rexp, (unsigned short*)pack, B, H, Lq, Lqp);
   rc = check_launch("a3d_attn16_bwd(prep)");
   if (rc) return rc;
-  static const int qt_env = getenv("A3D_ATTN_QT") ? atoi(getenv("A3D_ATTN_QT")) : 0;
-  const int QT = qt_env ? qt_env : (Lq > 64 ? 2 : 1);
-  const int KT = qt_env ? qt_env : (((size_t)B * H * (Sp / 128) >= 1024 && Lq > 16) ? 2 : 1);
-  const dim3 gq(xcd_grid(B * H, cdiv(Lqp, 64 * QT) * nsplit)), gk(xcd_grid(B * H, cdiv(Sp, 64 * KT)));
-  const unsigned long long* nostate = nullptr;
-  static const bool fast = getenv("A3D_ATTN_FAST") && atoi(getenv("A3D_ATTN_FAST")) != 0;     // single-fp16 G
-#define A3D_L16Q_(DROPV, QTV, GPV, ST, SITE, THR, SC)                                                                     \
-  hipLaunchKernelGGL((attn16_bwd_dq_kernel<DROPV, QTV, GPV>), gq, dim3(256), 0, s, (const unsigned short*)Qr,            \
-                     (const unsigned short*)Kr, (const unsigned short*)Vr, kmask,                                         \
-                     (const unsigned short*)dOr, LSE2, D, rexp, dQp, B, H, Lq, Lqp, S, Sp, nsplit, ST, SITE, THR, SC)
-#define A3D_L16K_(DROPV, KTV, GPV, ST, SITE, THR, SC)                                                                     \
-  hipLaunchKernelGGL((attn16_bwd_dkv_kernel<DROPV, KTV, GPV>), gk, dim3(256), 0, s, (const unsigned short*)pack,         \
-                     (const unsigned short*)Kr, (const unsigned short*)Vr, kmask, dK, dV, B, H, Lqp, S, Sp, ST, SITE,    \
-                     THR, SC)
-#define A3D_L16Q(DROPV, QTV, ST, SITE, THR, SC) \
-  do { if (fast) A3D_L16Q_(DROPV, QTV, 1, ST, SITE, THR, SC); else A3D_L16Q_(DROPV, QTV, 2, ST, SITE, THR, SC); } while (0)
-#define A3D_L16K(DROPV, KTV, ST, SITE, THR, SC) \
-  do { if (fast) A3D_L16K_(DROPV, KTV, 1, ST, SITE, THR, SC); else A3D_L16K_(DROPV, KTV, 2, ST, SITE, THR, SC); } while (0)
-  if (drop) {
-    if (QT == 2) A3D_L16Q(true, 2, drop_state, drop_site, thr, dscale);
-    else A3D_L16Q(true, 1, drop_state, drop_site, thr, dscale);
-  } else {
-    if (QT == 2) A3D_L16Q(false, 2, nostate, 0u, 0u, 1.0f);
-    else A3D_L16Q(false, 1, nostate, 0u, 0u, 1.0f);
-  }
+  const AttnTiles t = attn_tiles(B, H, Lq, Lqp, Sp, nsplit);
+  const int GP = attn_fast() ? 1 : 2;                  // parts of G: single fp16 with A3D_ATTN_FAST=1
+  with_bool(d.state != nullptr, [&](auto drop) {
+    with_int<2, 1>(t.QT, [&](auto qt) {
+      with_int<1, 2>(GP, [&](auto gp) {
+        hipLaunchKernelGGL((attn16_bwd_dq_kernel<decltype(drop)::value, decltype(qt)::value, decltype(gp)::value>), t.gq, dim3(256), 0,
+                           s, (const unsigned short*)Qr, (const unsigned short*)Kr, (const unsigned short*)Vr, kmask,
+                           (const unsigned short*)dOr, LSE2, D, rexp, dQp, B, H, Lq, Lqp, S, Sp, nsplit, d.state, d.site, d.thr,
+                           d.scale);
+      });
+    });
+  });
   rc = check_launch("a3d_attn16_bwd(dq)");
   if (rc) return rc;
-  if (drop) {
-    if (KT == 2) A3D_L16K(true, 2, drop_state, drop_site, thr, dscale);
-    else A3D_L16K(true, 1, drop_state, drop_site, thr, dscale);
-  } else {
-    if (KT == 2) A3D_L16K(false, 2, nostate, 0u, 0u, 1.0f);
-    else A3D_L16K(false, 1, nostate, 0u, 0u, 1.0f);
-  }
-#undef A3D_L16Q
-#undef A3D_L16K
-#undef A3D_L16Q_
-#undef A3D_L16K_
+  with_bool(d.state != nullptr, [&](auto drop) {
+    with_int<2, 1>(t.KT, [&](auto kt) {
+      with_int<1, 2>(GP, [&](auto gp) {
+        hipLaunchKernelGGL((attn16_bwd_dkv_kernel<decltype(drop)::value, decltype(kt)::value, decltype(gp)::value>), t.gk, dim3(256), 0,
+                           s, (const unsigned short*)pack, (const unsigned short*)Kr, (const unsigned short*)Vr, kmask, dK, dV, B, H,
+                           Lqp, S, Sp, d.state, d.site, d.thr, d.scale);
+      });
+    });
+  });
   return check_launch("a3d_attn16_bwd(dkv)");
 }

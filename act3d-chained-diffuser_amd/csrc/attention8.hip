@@ -26,8 +26,8 @@
 // Staging: ONE LDS-DMA instruction per wave and 64-key chunk (lanes 0-15: 16 key rows, lanes 16-31: 4 value channels x 64
 // keys), ring of 4 buffers as in attention16.hip.
 #include "attn_ring.h"
+#include "attn_launch.h"
 #include "../../include/act3d_hip.h"
-#include <stdlib.h>
 
 namespace a3d {
 
@@ -370,7 +370,7 @@ extern "C" size_t a3d_attn8_operand_bytes(int B, int H, int Sp) {
 
 extern "C" int a3d_attn8_fwd(const void* Qr, const void* Kr, const void* Vp, void* ops8, const unsigned char* kmask, float* O,
                              float* LSE2, float* ws, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit, void* stream) {
-  int rc = attn16_check_shapes("a3d_attn8_fwd", B, H, Lq, Lqp, S, Sp, nsplit, 16);
+  int rc = attn_check_shapes("a3d_attn8_fwd", B, H, Lq, Lqp, S, Sp, nsplit, 16, MASKW * 32);
   if (rc) return rc;
   if (!Qr || !Kr || !Vp || !ops8 || !O || !LSE2 || (nsplit > 1 && !ws)) { set_error("a3d_attn8_fwd: null pointer"); return A3D_ERR_ARG; }
   if (((size_t)ops8 & 255) != 0) { set_error("a3d_attn8_fwd: ops8 must be 256-byte aligned"); return A3D_ERR_ARG; }
@@ -390,21 +390,14 @@ extern "C" int a3d_attn8_fwd(const void* Qr, const void* Kr, const void* Vp, voi
                      K8, V8, B, H, S, Sp);
   rc = check_launch("a3d_attn8_fwd(pack)");
   if (rc) return rc;
-  const size_t rows = (size_t)B * H * Lqp;
-  float* Op = ws;
-  float* Mp = ws ? ws + (size_t)nsplit * rows * HDP : nullptr;
-  float* Lp = ws ? Mp + (size_t)nsplit * rows : nullptr;
-  static const int qt_env = getenv("A3D_ATTN_QT") ? atoi(getenv("A3D_ATTN_QT")) : 0;
-  const int QT = qt_env ? qt_env : (Lq > 64 ? 2 : 1);
-  dim3 grid(xcd_grid(B * H, cdiv(Lqp, 64 * QT) * nsplit));
-  if (QT == 2)
-    hipLaunchKernelGGL((attn8_fwd_kernel<2>), grid, dim3(256), 0, s, (const unsigned short*)Qr, K8, V8, amax, kmask, O, LSE2, Op, Mp,
-                       Lp, B, H, Lq, Lqp, S, Sp, nsplit);
-  else
-    hipLaunchKernelGGL((attn8_fwd_kernel<1>), grid, dim3(256), 0, s, (const unsigned short*)Qr, K8, V8, amax, kmask, O, LSE2, Op, Mp,
-                       Lp, B, H, Lq, Lqp, S, Sp, nsplit);
+  const AttnWs w = attn_ws_carve(ws, B, H, Lqp, nsplit);
+  const AttnTiles t = attn_tiles(B, H, Lq, Lqp, Sp, nsplit);
+  with_int<2, 1>(t.QT, [&](auto qt) {
+    hipLaunchKernelGGL((attn8_fwd_kernel<decltype(qt)::value>), t.gq, dim3(256), 0, s, (const unsigned short*)Qr, K8, V8, amax, kmask,
+                       O, LSE2, w.Op, w.Mp, w.Lp, B, H, Lq, Lqp, S, Sp, nsplit);
+  });
   rc = check_launch("a3d_attn8_fwd");
   if (rc) return rc;
-  if (nsplit > 1) rc = attn16_launch_combine(Op, Mp, Lp, O, LSE2, B, H, Lq, Lqp, nsplit, s);
+  if (nsplit > 1) rc = attn16_launch_combine(w.Op, w.Mp, w.Lp, O, LSE2, B, H, Lq, Lqp, nsplit, s);
   return rc;
 }

@@ -13,9 +13,8 @@
 // interleave that leaves P / dS in B-operand order in registers: no score tile is staged through LDS.
 // Operand tensors (rope.hip / attn_bwd_prep): rows format [..][N][hi16|lo16] and planes format [..][2][16][N]
 // of q, k, v and dO.
-#include "a3d_common.h"
+#include "attn_launch.h"
 #include "../../include/act3d_hip.h"
-#include <stdlib.h>
 
 namespace a3d {
 
@@ -526,19 +525,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_bf16_kernel(
 
 using namespace a3d;
 
-static int attn_bwd_bf16_launch(const void* Qs, const void* Qt, const void* Ks, const void* Kt, const void* Vs,
+static int attn_bwd_bf16_launch(const char* fn, const void* Qs, const void* Qt, const void* Ks, const void* Kt, const void* Vs,
                                 const unsigned char* kmask, const float* O, const float* dO, const float* LSE,
                                 void* dOs, void* dOt, float* D, float* dQp, float* dK, float* dV, int B, int H,
                                 int Lq, int Lqp, int S, int Sp, int nsplit, const unsigned long long* drop_state,
-                                unsigned int drop_site, float drop_p, void* stream) {
-  if (B <= 0 || H <= 0 || Lq <= 0 || Lqp < Lq || (Lqp % 64) != 0 || S <= 0 || Sp < S || (Sp % 64) != 0 || nsplit < 1 ||
-      nsplit > 64) {
-    set_error("a3d_attn_bwd_bf16: bad argument (B=%d H=%d Lq=%d Lqp=%d S=%d Sp=%d nsplit=%d; Lqp, Sp %% 64 == 0)", B, H, Lq,
-              Lqp, S, Sp, nsplit);
-    return A3D_ERR_ARG;
-  }
+                                unsigned int drop_site, float drop_p, bool drop_required, void* stream) {
+  int rc = attn_check_shapes(fn, B, H, Lq, Lqp, S, Sp, nsplit, 64, 0);
+  if (rc) return rc;
+  AttnDrop d;
+  rc = attn_drop_decode(fn, drop_state, drop_site, drop_p, drop_required, &d);
+  if (rc) return rc;
   if (!Qs || !Qt || !Ks || !Kt || !Vs || !O || !dO || !LSE || !dOs || !dOt || !D || !dQp || !dK || !dV) {
-    set_error("a3d_attn_bwd_bf16: null pointer");
+    set_error("%s: null pointer", fn);
     return A3D_ERR_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -551,49 +549,27 @@ static int attn_bwd_bf16_launch(const void* Qs, const void* Qt, const void* Ks, 
   }
   hipLaunchKernelGGL(attn_bwd_prep_bf16_kernel, dim3(Lqp / 64, B), dim3(256), lds, s, dO, O, (unsigned short*)dOs,
                      (unsigned short*)dOt, D, B, H, Lq, Lqp);
-  int rc = check_launch("a3d_attn_bwd_bf16(prep)");
+  rc = check_launch("a3d_attn_bwd_bf16(prep)");
   if (rc) return rc;
-  const bool drop = drop_state != nullptr && drop_p > 0.f;
-  if (drop_state && !(drop_p >= 0.f && drop_p < 1.f)) {
-    set_error("a3d_attn_bwd_bf16_dropout: dropout probability %g outside [0, 1)", (double)drop_p);
-    return A3D_ERR_ARG;
-  }
-  const unsigned int thr = drop ? (unsigned int)lrintf(drop_p * 65536.0f) : 0u;
-  const float dscale = drop ? 1.0f / (1.0f - drop_p) : 1.0f;
-  // two query tiles per wave for dQ once the query set fills them; two key tiles per wave for dK / dV when there are
-  // enough 128-key workgroups left to fill the chip (A3D_ATTN_QT = 1 / 2 forces either form of both)
-  static const int qt_env = getenv("A3D_ATTN_QT") ? atoi(getenv("A3D_ATTN_QT")) : 0;
-  const int QT = qt_env ? qt_env : (Lq > 64 ? 2 : 1);
-  const int KT = qt_env ? qt_env : (((size_t)B * H * (Sp / 128) >= 1024 && Lq > 16) ? 2 : 1);
-  const dim3 gq(xcd_grid(B * H, cdiv(Lqp, 64 * QT) * nsplit)), gk(xcd_grid(B * H, cdiv(Sp, 64 * KT)));
-  const unsigned long long* nostate = nullptr;
-#define A3D_LAUNCH_DQ(DROPV, QTV, ST, SITE, THR, SC)                                                                        \
-  hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<DROPV, QTV>), gq, dim3(256), 0, s, (const unsigned short*)Qs,                \
-                     (const unsigned short*)Ks, (const unsigned short*)Kt, (const unsigned short*)Vs, kmask,               \
-                     (const unsigned short*)dOs, LSE, D, dQp, B, H, Lq, Lqp, S, Sp, nsplit, ST, SITE, THR, SC)
-#define A3D_LAUNCH_DKV(DROPV, KTV, ST, SITE, THR, SC)                                                                       \
-  hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<DROPV, KTV>), gk, dim3(256), 0, s, (const unsigned short*)Qs,               \
-                     (const unsigned short*)Qt, (const unsigned short*)Ks, (const unsigned short*)Vs, kmask,               \
-                     (const unsigned short*)dOs, (const unsigned short*)dOt, LSE, D, dK, dV, B, H, Lq, Lqp, S, Sp, ST,     \
-                     SITE, THR, SC)
-  if (drop) {
-    if (QT == 2) A3D_LAUNCH_DQ(true, 2, drop_state, drop_site, thr, dscale);
-    else A3D_LAUNCH_DQ(true, 1, drop_state, drop_site, thr, dscale);
-  } else {
-    if (QT == 2) A3D_LAUNCH_DQ(false, 2, nostate, 0u, 0u, 1.0f);
-    else A3D_LAUNCH_DQ(false, 1, nostate, 0u, 0u, 1.0f);
-  }
+  const AttnTiles t = attn_tiles(B, H, Lq, Lqp, Sp, nsplit);
+  with_bool(d.state != nullptr, [&](auto drop) {
+    with_int<2, 1>(t.QT, [&](auto qt) {
+      hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<decltype(drop)::value, decltype(qt)::value>), t.gq, dim3(256), 0, s,
+                         (const unsigned short*)Qs, (const unsigned short*)Ks, (const unsigned short*)Kt, (const unsigned short*)Vs,
+                         kmask, (const unsigned short*)dOs, LSE, D, dQp, B, H, Lq, Lqp, S, Sp, nsplit, d.state, d.site, d.thr,
+                         d.scale);
+    });
+  });
   rc = check_launch("a3d_attn_bwd_bf16(dq)");
   if (rc) return rc;
-  if (drop) {
-    if (KT == 2) A3D_LAUNCH_DKV(true, 2, drop_state, drop_site, thr, dscale);
-    else A3D_LAUNCH_DKV(true, 1, drop_state, drop_site, thr, dscale);
-  } else {
-    if (KT == 2) A3D_LAUNCH_DKV(false, 2, nostate, 0u, 0u, 1.0f);
-    else A3D_LAUNCH_DKV(false, 1, nostate, 0u, 0u, 1.0f);
-  }
-#undef A3D_LAUNCH_DQ
-#undef A3D_LAUNCH_DKV
+  with_bool(d.state != nullptr, [&](auto drop) {
+    with_int<2, 1>(t.KT, [&](auto kt) {
+      hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<decltype(drop)::value, decltype(kt)::value>), t.gk, dim3(256), 0, s,
+                         (const unsigned short*)Qs, (const unsigned short*)Qt, (const unsigned short*)Ks, (const unsigned short*)Vs,
+                         kmask, (const unsigned short*)dOs, (const unsigned short*)dOt, LSE, D, dK, dV, B, H, Lq, Lqp, S, Sp,
+                         d.state, d.site, d.thr, d.scale);
+    });
+  });
   return check_launch("a3d_attn_bwd_bf16(dkv)");
 }
 
@@ -601,8 +577,8 @@ extern "C" int a3d_attn_bwd_bf16(const void* Qs, const void* Qt, const void* Ks,
                                  const unsigned char* kmask, const float* O, const float* dO, const float* LSE,
                                  void* dOs, void* dOt, float* D, float* dQp, float* dK, float* dV, int B, int H,
                                  int Lq, int Lqp, int S, int Sp, int nsplit, void* stream) {
-  return attn_bwd_bf16_launch(Qs, Qt, Ks, Kt, Vs, kmask, O, dO, LSE, dOs, dOt, D, dQp, dK, dV, B, H, Lq, Lqp, S, Sp, nsplit,
-                              nullptr, 0u, 0.f, stream);
+  return attn_bwd_bf16_launch("a3d_attn_bwd_bf16", Qs, Qt, Ks, Kt, Vs, kmask, O, dO, LSE, dOs, dOt, D, dQp, dK, dV, B, H, Lq, Lqp, S,
+                              Sp, nsplit, nullptr, 0u, 0.f, false, stream);
 }
 
 extern "C" int a3d_attn_bwd_bf16_dropout(const void* Qs, const void* Qt, const void* Ks, const void* Kt, const void* Vs,
@@ -610,7 +586,6 @@ extern "C" int a3d_attn_bwd_bf16_dropout(const void* Qs, const void* Qt, const v
                                          void* dOs, void* dOt, float* D, float* dQp, float* dK, float* dV, int B, int H,
                                          int Lq, int Lqp, int S, int Sp, int nsplit, const unsigned long long* drop_state,
                                          unsigned int drop_site, float drop_p, void* stream) {
-  if (!drop_state) { set_error("a3d_attn_bwd_bf16_dropout: null dropout state"); return A3D_ERR_ARG; }
-  return attn_bwd_bf16_launch(Qs, Qt, Ks, Kt, Vs, kmask, O, dO, LSE, dOs, dOt, D, dQp, dK, dV, B, H, Lq, Lqp, S, Sp, nsplit,
-                              drop_state, drop_site, drop_p, stream);
+  return attn_bwd_bf16_launch("a3d_attn_bwd_bf16_dropout", Qs, Qt, Ks, Kt, Vs, kmask, O, dO, LSE, dOs, dOt, D, dQp, dK, dV, B, H, Lq,
+                              Lqp, S, Sp, nsplit, drop_state, drop_site, drop_p, true, stream);
 }

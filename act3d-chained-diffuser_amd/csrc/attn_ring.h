@@ -174,6 +174,5 @@ __device__ __forceinline__ f32x4 bias_of(unsigned int word, int g, int T) {
 // launches attn16_combine_kernel (attention16.hip): flash-decoding combine of `nsplit` partial results
 int attn16_launch_combine(const float* Op, const float* Mp, const float* Lp, float* O, float* LSE2, int B, int H, int Lq,
                           int Lqp, int nsplit, hipStream_t s);
-int attn16_check_shapes(const char* fn, int B, int H, int Lq, int Lqp, int S, int Sp, int nsplit, int qmod);
 
 }  // namespace a3d

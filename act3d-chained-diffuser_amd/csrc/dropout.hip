@@ -54,16 +54,6 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(unsigned char* __rest
 
 using namespace a3d;
 
-static int drop_params(const char* fn, float p, uint32_t* thr16, float* scale) {
-  if (!(p >= 0.f) || !(p < 1.f)) {
-    set_error("%s: dropout probability %g outside [0, 1)", fn, (double)p);
-    return A3D_ERR_ARG;
-  }
-  *thr16 = (uint32_t)lrintf(p * 65536.0f);
-  *scale = 1.0f / (1.0f - p);
-  return A3D_OK;
-}
-
 extern "C" int a3d_dropout(const float* x, float* y, size_t n, const unsigned long long* state, unsigned int site,
                            float p, void* stream) {
   if (!x || !y || !state) { set_error("a3d_dropout: null pointer"); return A3D_ERR_ARG; }

@@ -551,16 +551,6 @@ extern "C" int a3d_linear_fwd(const float* X, int ldx, const float* W, int ldw, 
   return check_launch("a3d_linear_fwd");
 }
 
-static int linear_drop_params(const char* fn, float p, uint32_t* thr16, float* scale) {     // as dropout.hip's drop_params
-  if (!(p >= 0.f) || !(p < 1.f)) {
-    set_error("%s: dropout probability %g outside [0, 1)", fn, (double)p);
-    return A3D_ERR_ARG;
-  }
-  *thr16 = (uint32_t)lrintf(p * 65536.0f);
-  *scale = 1.0f / (1.0f - p);
-  return A3D_OK;
-}
-
 // Y = dropout(act(X W^T + b)): the layer and the nn.Dropout behind it (layers.py:82-84,146,181, diffusion_head.py:46,183,193) in
 // one launch.  Same bits as a3d_linear_fwd + a3d_dropout(Y -> Y) -- which is also what runs when the epilogue does not apply
 // (N % 8 != 0, or a row count that the bf16x3 kernel of linear_split.hip serves).
@@ -574,7 +564,7 @@ extern "C" int a3d_linear_fwd_drop(const float* X, int ldx, const float* W, int 
   }
   if (act == 2 && !mask) { set_error("a3d_linear_fwd_drop: act=2 needs a mask"); return A3D_ERR_ARG; }
   uint32_t thr; float scale;
-  int rc = linear_drop_params("a3d_linear_fwd_drop", p, &thr, &scale);
+  int rc = drop_params("a3d_linear_fwd_drop", p, &thr, &scale);
   if (rc) return rc;
   if (M == 0) return A3D_OK;
   if ((N & 7) || linear_split_applicable(X, ldx, W, ldw, bias, Y, ldy, mask, ldm, M, N, K, act)) {
@@ -838,7 +828,7 @@ extern "C" int a3d_add_layernorm_bwd_drop(const float* A, const float* R, const 
     return A3D_ERR_ARG;
   }
   uint32_t thr; float scale;
-  int rc = linear_drop_params("a3d_add_layernorm_bwd_drop", p, &thr, &scale);
+  int rc = drop_params("a3d_add_layernorm_bwd_drop", p, &thr, &scale);
   if (rc) return rc;
   if (M == 0) return A3D_OK;
   if (E > 64 && E <= 128 && (E & 7) == 0 &&
