@@ -12,10 +12,11 @@ from .losses import LossAndMetrics, TrajectoryCriterion  # noqa: F401,E402
 from . import engine  # noqa: F401,E402
 from . import diffusion  # noqa: F401,E402
 from .diffusion import DiffusionPlanner, DiffusionHead  # noqa: F401,E402
-from .diffusion import rank_trajectories, TrajectoryRanking  # noqa: F401,E402
-from .diffusion import trajectory_clearance, TrajectoryClearance, SceneTrajectoryRanking  # noqa: F401,E402
-from .diffusion import guide_trajectories, guided_segments, Guidance  # noqa: F401,E402
-from .diffusion import traj_pins, prefix_pins, check_pins, TrajectoryPins, Pins  # noqa: F401,E402
+from . import trajectory  # noqa: F401,E402
+from .trajectory import rank_trajectories, TrajectoryRanking  # noqa: F401,E402
+from .trajectory import trajectory_clearance, TrajectoryClearance, SceneTrajectoryRanking  # noqa: F401,E402
+from .trajectory import guide_trajectories, guided_segments, Guidance  # noqa: F401,E402
+from .trajectory import traj_pins, prefix_pins, check_pins, TrajectoryPins, Pins  # noqa: F401,E402
 from . import actioner  # noqa: F401,E402
 from .actioner import Actioner  # noqa: F401,E402
 from . import data, trainers  # noqa: F401,E402

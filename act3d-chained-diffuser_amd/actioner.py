@@ -19,6 +19,7 @@ import random
 import torch
 
 from .diffusion import check_sampling_call, _graph_replay
+from .trajectory import check_trajectory_mask
 
 _TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight",
             "scene_mask", "clear_margin", "clear_skip", "guide", "solver_order", "lower_order_final", "pins")
@@ -181,8 +182,7 @@ class Actioner:
         if self._predict_trajectory:
             if trajectory_mask is None:
                 raise ValueError("predict_trajectory=True needs a trajectory_mask (B, L)")
-            if trajectory_mask.dim() != 2 or trajectory_mask.shape[0] != B:
-                raise ValueError("trajectory_mask must be (B, L) with B = %d, got %s" % (B, tuple(trajectory_mask.shape)))
+            check_trajectory_mask(trajectory_mask, B)
         if use_graph and self._predict_keypose and ghost_points is None and \
                 getattr(self._keypose_model, "ghost_sampler", "philox") != "philox":
             raise ValueError("use_graph=True needs the device ghost-point sampler (ghost_sampler='philox'): the host sampler copies "
@@ -236,8 +236,8 @@ class Actioner:
         "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps, select,
         rot_weight, scene_mask, clear_margin, clear_skip, guide, solver_order, lower_order_final, pins) go to compute_trajectory unchanged (a rule that weighs "clearance"
         scores the candidates against pcds[:, -1], and `guide` steers the waypoints off that cloud while they are drawn); with select the candidates are ranked on the device, "trajectory" is the
-        selected one (B, L, 8) and self.last_ranking mirrors the planner's; with pins (diffusion.check_pins, pose rows of action_dim
-        channels; diffusion.prefix_pins for a replan that keeps what the robot is executing) self.last_pins mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
+        selected one (B, L, 8) and self.last_ranking mirrors the planner's; with pins (trajectory.check_pins, pose rows of action_dim
+        channels; trajectory.prefix_pins for a replan that keeps what the robot is executing) self.last_pins mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
         and the sampling loop as graphs."""
         bad = [k for k in sample_kw if k not in _TRAJ_KW]
         if bad:

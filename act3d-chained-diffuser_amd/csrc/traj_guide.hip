@@ -7,12 +7,10 @@
 // -- two roundings before the scale, the bits of DiffusionPlanner.unnormalize_pos.
 //
 // Two launches.
-//   1  traj_guide_partial<RPT>   the decomposition of traj_clear_partial (point chunk x row tile x scene, lanes own rows, 512 points
-//      staged through LDS per pass, dropped points staged as +inf; traj_points.h), with two differences: the row's position is
-//      unnormalised from the signal on load, and a lane keeps (best d^2, index of that point), replaced on a strict < while it scans
-//      its points in ascending order, so the lowest index among equal distances stays.  Where spare waves split the points of a tile
-//      (npg point groups) their pairs meet in LDS and are compared as (d^2, index), lexicographically; the same pair goes to
-//      ws: d^2 [chunk][b][g][i] floats, then the indices [chunk][b][g][i] ints (2^31 - 1 = no counted point).
+//   1  traj_guide_partial<RPT>   the scan of traj_points.h (tc_scan_partial, the decomposition of traj_clear_partial) with two
+//      differences: the row's position is unnormalised from the signal on load, and the scan is INDEXED -- a lane keeps (best d^2,
+//      index of that point), the lowest index among equal distances stays, and the pair goes to ws: d^2 [chunk][b][g][i] floats,
+//      then the indices [chunk][b][g][i] ints (2^31 - 1 = no counted point).
 //   2  traj_guide_apply          one workgroup per TRAJECTORY (b, g), thread i = row i (L <= 256).  A ballot scan of the mask gives
 //      the rank j of a valid row and, through a rank -> row table in LDS, its valid neighbours; all world positions of the
 //      trajectory are put into LDS BEFORE any row is written (Jacobi).  Then per row: the minimum over the chunks (strict <
@@ -27,114 +25,35 @@
 // the tile split or the run.  No atomics.
 #include "traj_points.h"
 #include "../../include/act3d_hip.h"
-#include <limits.h>
 #include <math.h>
 
 namespace a3d {
 
 constexpr int TG_MAX_L = TC_THREADS;     // traj_guide_apply: one thread per row
-constexpr int TG_NONE = INT_MAX;         // index of "no counted point"
 
 __device__ __forceinline__ float tg_world(float x, float lo, float hi) {
 #pragma clang fp contract(off)
   return ((x + 1.f) * 0.5f) * (hi - lo) + lo;
 }
 
-struct TrajGuideArgs {
+struct TrajGuideArgs : TrajScan {    // ws: the partial minima, then [n_chunks][B][R] ints: the point's index
   float* traj;                     // [B][G][L][D] signals, xyz of the free rows updated in place
-  const unsigned char* tmask;      // [B][L]
   const unsigned char* cmask;      // [B G][L][D] or NULL
   const float* bounds;             // [2][3]
-  const float* scene;              // [B][C][3][n_pix]
-  const unsigned char* smask;      // [B][C][n_pix] or NULL
-  float* ws;                       // [n_chunks][B][R] partial minima of d^2, then [n_chunks][B][R] ints: the point's index
   float* nearest;                  // [B][R] or NULL
-  long long N;                     // points per scene = C * n_pix
-  int n_pix, n_chunks, chunk_pts, row_tiles, nrg;
-  int B, G, L, D;
+  int D;
   float margin, push, smooth;
   int skip_head, skip_tail;
 };
 
 template <int RPT>
 __global__ __launch_bounds__(TC_THREADS) void traj_guide_partial(const TrajGuideArgs a) {
-  __shared__ f32x4 pts[TC_TILE];
-  __shared__ float red[TC_THREADS * RPT];          // [npg][nrg 64 RPT]
-  __shared__ int redi[TC_THREADS * RPT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // blockIdx.x = (b * row_tiles + tile) * n_chunks + chunk
-  const int chunk = blockIdx.x % a.n_chunks;
-  const int bt = blockIdx.x / a.n_chunks;
-  const int tile = bt % a.row_tiles, b = bt / a.row_tiles;
-  const int R = a.G * a.L;
-  const int nrg = a.nrg, npg = 4 / nrg;
-  const int rg = wave % nrg, pg = wave / nrg;
-  const int RT = nrg * 64 * RPT;                   // row slots of this tile
-  const int slot0 = rg * 64 * RPT + lane;          // this lane's slots: slot0 + 64 k
-  const int row_base = tile * (TC_THREADS * RPT);
-
-  float px[RPT], py[RPT], pz[RPT], best[RPT];
-  int bidx[RPT];
-#pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    const int r = row_base + slot0 + 64 * k;
-    px[k] = py[k] = pz[k] = 0.f;
-    best[k] = INFINITY;
-    bidx[k] = TG_NONE;
-    if (r < R && !a.tmask[(size_t)b * a.L + r % a.L]) {
-      const float* x = a.traj + ((size_t)b * R + r) * a.D;
-      px[k] = tg_world(x[0], a.bounds[0], a.bounds[3]);
-      py[k] = tg_world(x[1], a.bounds[1], a.bounds[4]);
-      pz[k] = tg_world(x[2], a.bounds[2], a.bounds[5]);
-    }
-  }
-
-  const long long first = (long long)chunk * a.chunk_pts;
-  const long long last = min(a.N, first + a.chunk_pts);
-  const float* S = a.scene + (size_t)b * a.N * 3;
-  const unsigned char* M = a.smask ? a.smask + (size_t)b * a.N : nullptr;
-  for (long long base = first; base < last; base += TC_TILE) {
-    const int cnt = (int)min((long long)TC_TILE, last - base);
-    __syncthreads();                               // the previous pass has read pts
-    tc_stage_points(pts, S, M, base, cnt, a.n_pix, tid);
-    __syncthreads();
-    const int cnt_up = (cnt + 3) & ~3;             // whole groups of 4 points; TC_TILE is a multiple of 4 npg for npg <= 4
-    const int n0 = (int)base;                      // N < 2^31: a point's index fits an int
-    for (int j = pg * 4; j < cnt_up; j += 4 * npg) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const f32x4 s = pts[j + u];
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-          const float d2 = tc_dist2(px[k], py[k], pz[k], s);
-          const bool lt = d2 < best[k];            // strict, ascending scan: the lowest index of a tie stays; +inf and NaN never win
-          best[k] = lt ? d2 : best[k];
-          bidx[k] = lt ? n0 + j + u : bidx[k];
-        }
-      }
-    }
-  }
-
-#pragma unroll
-  for (int k = 0; k < RPT; ++k) {
-    red[pg * RT + slot0 + 64 * k] = best[k];
-    redi[pg * RT + slot0 + 64 * k] = bidx[k];
-  }
-  __syncthreads();
-  const size_t plane = (size_t)a.n_chunks * a.B * R;
-  float* out = a.ws + ((size_t)chunk * a.B + b) * R;
-  int* outi = (int*)(a.ws + plane) + ((size_t)chunk * a.B + b) * R;
-  for (int s = tid; s < RT; s += TC_THREADS) {
-    float m = red[s];
-    int mi = redi[s];
-    for (int q = 1; q < npg; ++q) {                // the point groups interleave their indices: (d^2, index) lexicographically
-      const float d = red[q * RT + s];
-      const int di = redi[q * RT + s];
-      if (d < m || (d == m && di < mi)) { m = d; mi = di; }
-    }
-    const int r = row_base + s;
-    if (r < R) { out[r] = m; outi[r] = mi; }
-  }
+  tc_scan_partial<RPT, true>(a, [&a](int b, int r, float& x, float& y, float& z) {
+    const float* s = a.traj + ((size_t)b * (a.G * a.L) + r) * a.D;
+    x = tg_world(s[0], a.bounds[0], a.bounds[3]);
+    y = tg_world(s[1], a.bounds[1], a.bounds[4]);
+    z = tg_world(s[2], a.bounds[2], a.bounds[5]);
+  });
 }
 
 __global__ __launch_bounds__(TC_THREADS) void traj_guide_apply(const TrajGuideArgs a) {
@@ -172,7 +91,7 @@ __global__ __launch_bounds__(TC_THREADS) void traj_guide_apply(const TrajGuideAr
 
   // ---- the nearest counted point: minimum over the chunks, ascending, strict <
   float d2 = INFINITY;
-  int idx = TG_NONE;
+  int idx = TC_NONE;
   if (valid && finite) {
     const size_t plane = (size_t)a.n_chunks * a.B * R;
     for (int c = 0; c < a.n_chunks; ++c) {
@@ -190,7 +109,7 @@ __global__ __launch_bounds__(TC_THREADS) void traj_guide_apply(const TrajGuideAr
   float add[3] = {0.f, 0.f, 0.f};
   {
 #pragma clang fp contract(off)
-    if (a.push > 0.f && idx != TG_NONE && d > 0.f && d < a.margin) {
+    if (a.push > 0.f && idx != TC_NONE && d > 0.f && d < a.margin) {
       const long long c = idx / a.n_pix, q = idx - c * a.n_pix;
       const float* s = a.scene + (size_t)b * a.N * 3 + (size_t)c * 3 * a.n_pix + q;
       const float w = a.push * (a.margin - d) / d;
@@ -217,9 +136,7 @@ __global__ __launch_bounds__(TC_THREADS) void traj_guide_apply(const TrajGuideAr
 using namespace a3d;
 
 extern "C" size_t a3d_traj_guide_ws_floats(int B, int G, int L, int n_points, int n_chunks) {
-  if (B <= 0 || G <= 0 || L <= 0 || n_points <= 0 || n_chunks < 0) return 0;
-  const int c = tc_chunks(B, G, L, n_points, n_chunks);
-  return 2 * (size_t)c * B * G * L;
+  return 2 * tc_ws_plane(B, G, L, n_points, n_chunks);          // the index plane behind the d^2 plane
 }
 
 extern "C" int a3d_traj_guide(float* traj, int D, const unsigned char* tmask, const unsigned char* cond_mask, const float* bounds,
@@ -227,41 +144,22 @@ extern "C" int a3d_traj_guide(float* traj, int D, const unsigned char* tmask, co
                               int skip_tail, float push, float smooth, float* nearest, float* ws, int n_chunks, int B, int G, int L,
                               void* stream) {
   const char* me = "a3d_traj_guide";
-  if (!traj || !tmask || !bounds || !scene || !ws) {
-    set_error("%s: null pointer (traj, tmask, bounds, scene and ws are required)", me); return A3D_ERR_ARG;
-  }
-  if (B <= 0 || G <= 0 || L <= 0) { set_error("%s: B, G and L must be positive (B=%d G=%d L=%d)", me, B, G, L); return A3D_ERR_ARG; }
-  if (n_cam <= 0 || n_pix <= 0) { set_error("%s: n_cam and n_pix must be positive (n_cam=%d n_pix=%d)", me, n_cam, n_pix); return A3D_ERR_ARG; }
-  if (G > TC_MAX_G) { set_error("%s: G=%d exceeds %d candidates per scene", me, G, TC_MAX_G); return A3D_ERR_ARG; }
+  TrajGuideArgs a;
+  int rpt;
+  unsigned blocks;
+  int rc = tc_scan_plan(me, traj && tmask && bounds && scene && ws, "traj, tmask, bounds, scene and ws", &a, &rpt, &blocks, tmask, scene,
+                        scene_mask, ws, n_cam, n_pix, margin, skip_head, skip_tail, n_chunks, B, G, L);
+  if (rc) return rc;
   if (L > TG_MAX_L) { set_error("%s: L=%d exceeds %d rows per trajectory", me, L, TG_MAX_L); return A3D_ERR_ARG; }
   if (D != 9 && D != 10) { set_error("%s: D=%d, signal rows have 9 or 10 channels", me, D); return A3D_ERR_ARG; }
-  if (!(margin > 0.f && margin <= FLT_MAX)) { set_error("%s: margin must be finite and positive", me); return A3D_ERR_ARG; }
-  if (skip_head < 0 || skip_tail < 0) { set_error("%s: negative skip (skip_head=%d skip_tail=%d)", me, skip_head, skip_tail); return A3D_ERR_ARG; }
-  if (n_chunks < 0) { set_error("%s: n_chunks=%d is negative (0 = chosen by the entry)", me, n_chunks); return A3D_ERR_ARG; }
   if (!(push >= 0.f && push <= 1.f) || !(smooth >= 0.f && smooth <= 1.f)) {
     set_error("%s: push and smooth must lie in [0, 1] (push=%g smooth=%g)", me, (double)push, (double)smooth); return A3D_ERR_ARG;
   }
   if (push == 0.f && smooth == 0.f) { set_error("%s: push and smooth are both 0: nothing to do", me); return A3D_ERR_ARG; }
-  const long long N = (long long)n_cam * n_pix, R = (long long)G * L;
-  if (N > 0x7fffffffLL) { set_error("%s: n_cam * n_pix overflows int (n_cam=%d n_pix=%d)", me, n_cam, n_pix); return A3D_ERR_ARG; }
-  if (B > 65535) { set_error("%s: B=%d exceeds 65535 scenes per call", me, B); return A3D_ERR_ARG; }
-  TrajGuideArgs a;
-  a.traj = traj; a.tmask = tmask; a.cmask = cond_mask; a.bounds = bounds; a.scene = scene; a.smask = scene_mask; a.ws = ws;
-  a.nearest = nearest;
-  a.N = N; a.n_pix = n_pix;
-  a.n_chunks = tc_chunks(B, G, L, N, n_chunks);
-  a.chunk_pts = (int)((N + a.n_chunks - 1) / a.n_chunks);
-  int rpt;
-  tc_shape(R, &rpt, &a.nrg, &a.row_tiles);
-  a.B = B; a.G = G; a.L = L; a.D = D;
+  a.traj = traj; a.cmask = cond_mask; a.bounds = bounds; a.nearest = nearest; a.D = D;
   a.margin = margin; a.push = push; a.smooth = smooth; a.skip_head = skip_head; a.skip_tail = skip_tail;
-  const long long blocks = (long long)a.n_chunks * a.row_tiles * B;
-  if (blocks > 0x7fffffffLL) { set_error("%s: %lld workgroups (n_chunks=%d) exceed the grid", me, blocks, a.n_chunks); return A3D_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
-  if (rpt == 1) hipLaunchKernelGGL(traj_guide_partial<1>, dim3((unsigned)blocks), dim3(TC_THREADS), 0, s, a);
-  else if (rpt == 2) hipLaunchKernelGGL(traj_guide_partial<2>, dim3((unsigned)blocks), dim3(TC_THREADS), 0, s, a);
-  else hipLaunchKernelGGL(traj_guide_partial<4>, dim3((unsigned)blocks), dim3(TC_THREADS), 0, s, a);
-  const int rc = check_launch(me);
+  rc = tc_scan_launch(me, rpt, blocks, a, s, traj_guide_partial<1>, traj_guide_partial<2>, traj_guide_partial<4>);
   if (rc) return rc;
   hipLaunchKernelGGL(traj_guide_apply, dim3((unsigned)(B * G)), dim3(TC_THREADS), 0, s, a);
   return check_launch(me);

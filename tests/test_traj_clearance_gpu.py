@@ -147,6 +147,38 @@ def test_kernel_vs_float64_restatement(a3d, dev, shape, mask_kind, with_mask, Dp
     assert np.array_equal(got["selected"].cpu().numpy(), ref["selected"]), name
 
 
+# G L = 1088 rows: two row tiles of 1024 slots (4 per lane), the second holds 64 rows -- the only shape here whose tile index is not 0;
+# 21 points: less than one staged tile, n_chunks = 3 gives chunks of 7
+TWO_TILES = (1, 64, 17, 1, 3, 7)
+
+
+@pytest.mark.parametrize("with_mask", [False, True], ids=["all-points", "scene-mask"])
+@pytest.mark.parametrize("mask_kind", R.MASKS)
+def test_two_row_tiles_vs_float64_restatement(a3d, dev, mask_kind, with_mask):
+    """nearest and clearance of the second row tile (rows 1024 .. 1087), the bars of this file; no ranking, so no condition on gaps"""
+    P, mask, _, _, S, sm = C.make_inputs(0, *TWO_TILES, 8, mask_kind)
+    sm = sm if with_mask else None
+    name = "traj_clearance two tiles %s %s" % (mask_kind, "scene-mask" if with_mask else "all-points")
+    assert P.shape[1] * P.shape[2] == 1024 + 64
+    near_ref, clear_ref = C.clearance_ref(P, mask, S, sm)
+    Pd, md, Sd, smd = t(P, dev), t(mask, dev, np.uint8), t(S, dev), t(sm, dev, np.uint8)
+    near, clear, ok = raw_clearance(a3d, Pd, md, Sd, smd)
+    assert ok, name + ": guard bands"
+    n_err = check_nearest(near, near_ref, name)
+    got = clear.cpu().numpy().astype(np.float64)
+    assert np.array_equal(np.isnan(got), np.isnan(clear_ref)), name
+    fin = ~np.isnan(clear_ref)
+    c_err = float(np.abs(got[fin] - clear_ref[fin]).max()) if fin.any() else 0.0
+    print("[parity] %s: nearest max_rel_err %.2e (bar %.0e), clearance max_abs_err %.2e (bar %.0e), finite rows of tile 1: %d" % (
+        name, n_err, NEAR_RTOL, c_err, CLEAR_ATOL, int(np.isfinite(near_ref.reshape(-1)[1024:]).sum())))
+    assert n_err <= NEAR_RTOL, "%s: nearest max rel err %.3e > %g" % (name, n_err, NEAR_RTOL)
+    assert c_err <= CLEAR_ATOL, "%s: clearance max abs err %.3e > %g" % (name, c_err, CLEAR_ATOL)
+    for chunks in (1, 3, 0):
+        n2, c2, ok2 = raw_clearance(a3d, Pd, md, Sd, smd, n_chunks=chunks)
+        assert ok2 and torch.equal(n2.view(torch.int32), near.view(torch.int32)) and torch.equal(c2.view(torch.int32), clear.view(torch.int32)), \
+            "%s: n_chunks=%d" % (name, chunks)
+
+
 # ------------------------------------------------------------------------------------------------ 2: special values
 def test_no_counted_point_padded_rows_nan_rows_and_eaten_skips(a3d, dev):
     (P, mask, goal, bounds, S, sm), _ = case((2, 4, 17, 3, 16, 16), "scattered", 8, True)

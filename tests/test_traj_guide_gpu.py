@@ -118,6 +118,39 @@ def test_kernel_vs_float64_restatement(a3d, dev, shape, mask_kind, with_mask, D)
             assert ok2 and torch.equal(bits(g2), bits(got)) and torch.equal(bits(n2), bits(near)), "%s: n_chunks=%d" % (name, chunks)
 
 
+# G L = 1088 rows: two row tiles of 1024 slots (4 per lane), the second holds 64 rows -- the only shape here whose tile index is not 0
+TWO_TILES = (1, 64, 17, 1, 3, 7)
+
+
+@pytest.mark.parametrize("with_mask", [False, True], ids=["all-points", "scene-mask"])
+@pytest.mark.parametrize("mask_kind", GR.MASKS)
+def test_two_row_tiles_vs_float64_restatement(a3d, dev, mask_kind, with_mask):
+    """x' and nearest of the second row tile (rows 1024 .. 1087), D = 9, push 1, smooth 0.5, the bars and the condition of this file"""
+    P, mask, bounds, S, sm, cm = GR.make_inputs(SEED, *TWO_TILES, 9, mask_kind)
+    sm = sm if with_mask else None
+    push, smooth = 1.0, 0.5
+    name = "traj_guide two tiles %s %s" % (mask_kind, "scene-mask" if with_mask else "all-points")
+    Pd, md, bd, Sd, smd, cmd = t(P, dev), t(mask, dev, np.uint8), t(bounds, dev), t(S, dev), t(sm, dev, np.uint8), t(cm, dev)
+    X = a3d.diffusion.pose_to_signal(Pd, bd)
+    assert X.shape == (1, 64, 17, 9) and X.shape[1] * X.shape[2] == 1024 + 64
+    ref = GR.guide_ref(X.cpu().numpy(), mask, cm, bounds, S, sm, push=push, smooth=smooth)
+    ties, n_push, d_min = GR.conditions(ref)
+    assert ties <= 0.02 * n_push and d_min >= 1e-4, "%s: the case misses the condition (%d near ties of %d pushed rows, d_min %.2e)" % (
+        name, ties, n_push, d_min)
+    got, near, ok = raw_guide(a3d, X, md, cmd, bd, Sd, smd, push=push, smooth=smooth)
+    assert ok, name + ": guard bands"
+    worst, via_alt = check_against(got, X, ref, GR.row_bar(ref, bounds, GR.MARGIN, push, smooth), name)
+    n_err = check_nearest(near, ref["nearest"], name)
+    print("[parity] %s: x' max err / bar %.3f (bar = 4 x bound), nearest max_rel_err %.2e (bar %.0e), free rows %d (tile 1: %d), pushed %d "
+          "(tile 1: %d), near ties %d (matched through an alternative: %d)" % (
+              name, worst, n_err, NEAR_RTOL, int(ref["free"].sum()), int(ref["free"].reshape(-1)[1024:].sum()), n_push,
+              int(ref["pushed"].reshape(-1)[1024:].sum()), ties, via_alt))
+    assert n_err <= NEAR_RTOL, "%s: nearest max rel err %.3e > %g" % (name, n_err, NEAR_RTOL)
+    for chunks in (1, 3, 0):
+        g2, n2, ok2 = raw_guide(a3d, X, md, cmd, bd, Sd, smd, n_chunks=chunks, push=push, smooth=smooth)
+        assert ok2 and torch.equal(bits(g2), bits(got)) and torch.equal(bits(n2), bits(near)), "%s: n_chunks=%d" % (name, chunks)
+
+
 # ------------------------------------------------------------------------------------------------ 2: the tie rule and special values
 def test_an_exact_tie_goes_to_the_lower_index_across_lanes_groups_passes_and_chunks(a3d, dev):
     """bounds (-1, 1): world == normalised, every value below is exact in fp32.  Two points exactly 0.25 from the row, everything
