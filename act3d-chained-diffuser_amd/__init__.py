@@ -16,6 +16,7 @@ from . import trajectory  # noqa: F401,E402
 from .trajectory import rank_trajectories, TrajectoryRanking  # noqa: F401,E402
 from .trajectory import trajectory_clearance, TrajectoryClearance, SceneTrajectoryRanking  # noqa: F401,E402
 from .trajectory import guide_trajectories, guided_segments, Guidance  # noqa: F401,E402
+from .trajectory import body_clearance, check_body, GripperBody  # noqa: F401,E402
 from .trajectory import traj_pins, prefix_pins, check_pins, TrajectoryPins, Pins  # noqa: F401,E402
 from . import actioner  # noqa: F401,E402
 from .actioner import Actioner  # noqa: F401,E402

@@ -22,7 +22,7 @@ from .diffusion import check_sampling_call, _graph_replay
 from .trajectory import check_trajectory_mask
 
 _TRAJ_KW = ("num_samples", "num_inference_steps", "scheduler", "eta", "init_noise", "step_noise", "n_steps", "select", "rot_weight",
-            "scene_mask", "clear_margin", "clear_skip", "guide", "solver_order", "lower_order_final", "pins")
+            "scene_mask", "clear_margin", "clear_skip", "guide", "solver_order", "lower_order_final", "pins", "clear_body")
 
 
 def _same_tensors(a, b):
@@ -234,8 +234,8 @@ class Actioner:
         (B, history, >= action_dim), read only with predict_keypose=False; trajectory_mask (B, L), needed with
         predict_trajectory=True.  Returns {"action": (B, 8) or gt_action[:, -1], "trajectory": compute_trajectory's result or None,
         "attention": {}}.  sample_kw (num_samples, num_inference_steps, scheduler, eta, init_noise, step_noise, n_steps, select,
-        rot_weight, scene_mask, clear_margin, clear_skip, guide, solver_order, lower_order_final, pins) go to compute_trajectory unchanged (a rule that weighs "clearance"
-        scores the candidates against pcds[:, -1], and `guide` steers the waypoints off that cloud while they are drawn); with select the candidates are ranked on the device, "trajectory" is the
+        rot_weight, scene_mask, clear_margin, clear_skip, guide, solver_order, lower_order_final, pins, clear_body) go to compute_trajectory unchanged (a rule that weighs "clearance"
+        scores the candidates against pcds[:, -1] -- with clear_body, a gripper body of swept spheres (trajectory.body_clearance), instead of the tool point -- and `guide` steers the waypoints off that cloud while they are drawn); with select the candidates are ranked on the device, "trajectory" is the
         selected one (B, L, 8) and self.last_ranking mirrors the planner's; with pins (trajectory.check_pins, pose rows of action_dim
         channels; trajectory.prefix_pins for a replan that keeps what the robot is executing) self.last_pins mirrors the planner's; ghost_points to Act3D; use_graph replays the keypose half
         and the sampling loop as graphs."""

@@ -14,14 +14,14 @@ LIB_PATH = os.path.join(PKG_DIR, _OUT)
 if _OUT != "libact3d_hip.so":
     OBJ_DIR = os.path.join(CSRC, "obj_" + _OUT[len("libact3d_hip_"):-3])
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
-SOURCES = ["api.hip", "linear.hip", "linear_split.hip", "rope.hip", "ctx_proj.hip", "attention.hip", "attention_bwd.hip", "attention16.hip", "attention8.hip", "scene.hip", "heads.hip", "optim.hip", "diffusion.hip", "traj_rank.hip", "traj_clearance.hip", "traj_guide.hip", "traj_pins.hip", "vision.hip", "dropout.hip", "denoise.hip", "single_query.hip", "single_query_wave.hip", "query_stream.hip", "data.hip", "conv1x1.hip", "conv1x1_deep.hip", "bn_gram.hip", "conv3x3.hip", "fpn_sparse.hip", "stem.hip"]
+SOURCES = ["api.hip", "linear.hip", "linear_split.hip", "rope.hip", "ctx_proj.hip", "attention.hip", "attention_bwd.hip", "attention16.hip", "attention8.hip", "scene.hip", "heads.hip", "optim.hip", "diffusion.hip", "traj_rank.hip", "traj_clearance.hip", "traj_body.hip", "traj_guide.hip", "traj_pins.hip", "vision.hip", "dropout.hip", "denoise.hip", "single_query.hip", "single_query_wave.hip", "query_stream.hip", "data.hip", "conv1x1.hip", "conv1x1_deep.hip", "bn_gram.hip", "conv3x3.hip", "fpn_sparse.hip", "stem.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # The attention kernels never produce NaNs on their own (masked rows are handled explicitly, -inf only enters exp2):
 # without IEEE-mode sNaN quieting hipcc drops the canonicalising v_max_f32 x, x it otherwise puts in front of every fmaxf
 # on an MFMA result (12 of 108 VALU instructions per 64-key chunk of the VALU-bound forward loop).
 _ATTN_FLAGS = ["-fno-honor-nans", "-mno-amdgpu-ieee"]
 EXTRA_FLAGS = {"attention.hip": _ATTN_FLAGS, "attention_bwd.hip": _ATTN_FLAGS, "attention16.hip": _ATTN_FLAGS,
-               "attention8.hip": _ATTN_FLAGS, "traj_clearance.hip": ["-Wall", "-Wextra"],
+               "attention8.hip": _ATTN_FLAGS, "traj_clearance.hip": ["-Wall", "-Wextra"], "traj_body.hip": ["-Wall", "-Wextra"],
                "traj_guide.hip": ["-Wall", "-Wextra"], "traj_pins.hip": ["-Wall", "-Wextra"], "optim.hip": ["-Wall", "-Wextra"]}
 
 

@@ -48,7 +48,7 @@ struct TrajGuideArgs : TrajScan {    // ws: the partial minima, then [n_chunks][
 
 template <int RPT>
 __global__ __launch_bounds__(TC_THREADS) void traj_guide_partial(const TrajGuideArgs a) {
-  tc_scan_partial<RPT, true>(a, [&a](int b, int r, float& x, float& y, float& z) {
+  tc_scan_partial<RPT, true, false>(a, [&a](int b, int r, float& x, float& y, float& z) {
     const float* s = a.traj + ((size_t)b * (a.G * a.L) + r) * a.D;
     x = tg_world(s[0], a.bounds[0], a.bounds[3]);
     y = tg_world(s[1], a.bounds[1], a.bounds[4]);

@@ -1,6 +1,8 @@
-// The brute-force pass over a scene cloud that traj_clearance.hip (the nearest distance) and traj_guide.hip (the nearest point) share:
-// the decomposition (point chunk x row tile x scene, lanes own rows), the staging of 512 points through LDS, d^2 of a pair, the scan
-// itself (tc_scan_partial) and the host side of its launch: the argument checks, the tile split and the chunking (tc_scan_plan).
+// The brute-force pass over a scene cloud that traj_clearance.hip (the nearest distance), traj_guide.hip (the nearest point) and
+// traj_body.hip (the nearest distance of swept spheres) share: the decomposition (point chunk x row tile x scene, lanes own rows), the
+// staging of 512 points through LDS, d^2 of a pair for the two kinds of row (a point, tc_dist2; a segment, tc_seg_dist2), the scan itself
+// (tc_scan_partial) and the host side of its launch: the argument checks, the tile split and the chunking (tc_scan_plan); and what the
+// one-workgroup-per-scene stages share: the ranks of the valid rows (tc_rank_rows) and the hinge mean per candidate (tc_hinge_mean).
 #pragma once
 #include "a3d_common.h"
 #include <float.h>
@@ -23,7 +25,7 @@ struct TrajScan {
   float* ws;                       // [n_chunks][B][R] partial minima of d^2, then the entry's own tail
   long long N;                     // points per scene = C * n_pix
   int n_pix, n_chunks, chunk_pts, row_tiles, nrg;
-  int B, G, L;
+  int B, G, L;                     // G: row groups of L rows per scene (candidates, or candidates x spheres)
 };
 
 __device__ __forceinline__ bool tc_finite(float v) { return fabsf(v) <= FLT_MAX; }
@@ -32,6 +34,18 @@ __device__ __forceinline__ float tc_dist2(float px, float py, float pz, const f3
 #pragma clang fp contract(off)
   const float dx = px - s[0], dy = py - s[1], dz = pz - s[2];
   return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
+
+// d^2 of a counted point s and the segment a + t d, t in [0, 1]; inv = 1 / |d|^2, or 0 when |d|^2 == 0 (the segment is the point a:
+// t is then 0 or 1, w = u either way, and the result has the bits of tc_dist2).  fminf / fmaxf with the constant as the second operand
+// return the constant for a NaN t (a dropped point [+inf 0 0] gives inf * 0), so t is always finite and w[0] = +inf - t d[0] = +inf:
+// d^2 of a dropped point is +inf, never NaN.
+__device__ __forceinline__ float tc_seg_dist2(float ax, float ay, float az, float dx, float dy, float dz, float inv, const f32x4 s) {
+#pragma clang fp contract(off)
+  const float ux = s[0] - ax, uy = s[1] - ay, uz = s[2] - az;
+  const float t = fmaxf(fminf(fmaf(uz, dz, fmaf(uy, dy, ux * dx)) * inv, 1.f), 0.f);
+  const float wx = fmaf(-t, dx, ux), wy = fmaf(-t, dy, uy), wz = fmaf(-t, dz, uz);
+  return fmaf(wz, wz, fmaf(wy, wy, wx * wx));
 }
 
 // Points base .. base + cnt - 1 of one scene ([C][3][n_pix], mask [C][n_pix] or NULL) into pts[TC_TILE] as [x y z 0]; a masked or
@@ -54,13 +68,15 @@ __device__ __forceinline__ void tc_stage_points(f32x4* pts, const float* S, cons
 }
 
 // The whole body of a partial kernel: grid (point chunk x row tile x scene), TC_THREADS threads.  Lanes own rows (RPT rows per lane,
-// their running minima of d^2 in registers); pos(b, r, x, y, z) loads the world position of row r of scene b.  A row tile has
+// their running minima of d^2 in registers); the kind of row is a point, pos(b, r, x, y, z) loads the world position of row r of scene b, or
+// (SEGMENT) a segment, pos(b, r, ax, ay, az, dx, dy, dz, inv) loads its start, its direction and 1 / |d|^2: 7 registers per row slot
+// instead of 3, tc_seg_dist2 instead of tc_dist2, everything else is shared.  A row tile has
 // 256 RPT row slots; where a scene has fewer than 4 waves' worth of rows the spare waves take every second / fourth group of 4 points
 // of the tile instead (nrg row groups x npg point groups = 4 waves) and the groups' minima meet in LDS.  Partial minima go to
 // ws[chunk][b][r].  INDEXED: a lane keeps (best d^2, index of that point), replaced on a strict < while it scans its points in
 // ascending order, so the lowest index among equal distances stays; the point groups' pairs are compared as (d^2, index),
 // lexicographically, and the indices go to the plane behind the d^2 plane, [chunk][b][r] ints (TC_NONE = no counted point).
-template <int RPT, bool INDEXED, class Pos>
+template <int RPT, bool INDEXED, bool SEGMENT, class Pos>
 __device__ __forceinline__ void tc_scan_partial(const TrajScan& a, Pos pos) {
   __shared__ f32x4 pts[TC_TILE];
   __shared__ float red[TC_THREADS * RPT];          // [npg][nrg 64 RPT]
@@ -78,6 +94,7 @@ __device__ __forceinline__ void tc_scan_partial(const TrajScan& a, Pos pos) {
   const int row_base = tile * (TC_THREADS * RPT);
 
   float px[RPT], py[RPT], pz[RPT], best[RPT];
+  float qx[SEGMENT ? RPT : 1], qy[SEGMENT ? RPT : 1], qz[SEGMENT ? RPT : 1], qi[SEGMENT ? RPT : 1];      // a segment's d and inv
   int bidx[RPT];
 #pragma unroll
   for (int k = 0; k < RPT; ++k) {
@@ -85,7 +102,12 @@ __device__ __forceinline__ void tc_scan_partial(const TrajScan& a, Pos pos) {
     px[k] = py[k] = pz[k] = 0.f;
     best[k] = INFINITY;
     bidx[k] = TC_NONE;
-    if (r < R && !a.tmask[(size_t)b * a.L + r % a.L]) pos(b, r, px[k], py[k], pz[k]);
+    if constexpr (SEGMENT) {
+      qx[k] = qy[k] = qz[k] = qi[k] = 0.f;
+      if (r < R && !a.tmask[(size_t)b * a.L + r % a.L]) pos(b, r, px[k], py[k], pz[k], qx[k], qy[k], qz[k], qi[k]);
+    } else {
+      if (r < R && !a.tmask[(size_t)b * a.L + r % a.L]) pos(b, r, px[k], py[k], pz[k]);
+    }
   }
 
   const long long first = (long long)chunk * a.chunk_pts;
@@ -105,7 +127,9 @@ __device__ __forceinline__ void tc_scan_partial(const TrajScan& a, Pos pos) {
         const f32x4 s = pts[j + u];
 #pragma unroll
         for (int k = 0; k < RPT; ++k) {
-          const float d2 = tc_dist2(px[k], py[k], pz[k], s);
+          float d2;
+          if constexpr (SEGMENT) d2 = tc_seg_dist2(px[k], py[k], pz[k], qx[k], qy[k], qz[k], qi[k], s);
+          else d2 = tc_dist2(px[k], py[k], pz[k], s);
           if constexpr (INDEXED) {
             const bool lt = d2 < best[k];          // strict, ascending scan: the lowest index of a tie stays; +inf and NaN never win
             best[k] = lt ? d2 : best[k];
@@ -146,6 +170,77 @@ __device__ __forceinline__ void tc_scan_partial(const TrajScan& a, Pos pos) {
   }
 }
 
+// The ranks of the valid rows of one mask row m[L], by all TC_THREADS threads of a workgroup: returns n = the valid rows and calls
+// each(i, valid, j, n) once for every row i < L with j = its rank among the valid rows (meaningless where !valid), 256 rows per pass.
+// Ends with a barrier: what each() stored, LDS or global, is ordered for the whole workgroup.
+template <class Each>
+__device__ __forceinline__ int tc_rank_rows(const unsigned char* m, int L, Each each) {
+  __shared__ int wsum[4];
+  __shared__ int carry;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  {
+    int cnt = 0;
+    for (int i = tid; i < L; i += TC_THREADS) cnt += m[i] ? 0 : 1;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (lane == 0) wsum[wave] = cnt;
+    if (tid == 0) carry = 0;
+  }
+  __syncthreads();
+  const int n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  __syncthreads();
+  for (int i0 = 0; i0 < L; i0 += TC_THREADS) {
+    const int i = i0 + tid;
+    const bool valid = i < L && !m[i];
+    const unsigned long long bal = __ballot(valid);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[wave] = __popcll(bal);
+    __syncthreads();
+    int j = carry + before;
+    for (int w = 0; w < wave; ++w) j += wsum[w];
+    if (i < L) each(i, valid, j, n);
+    __syncthreads();
+    if (tid == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+  }
+  return n;
+}
+
+// The last stage of a clearance entry, by all TC_THREADS threads of the scene's workgroup: near_of(g, i) is the distance of valid row i
+// of candidate g (NaN = not finite); nearest ([G][L] of the scene, or NULL) gets it, +inf on the rows m pads; clearance[g] = the mean
+// over the rows with scored[i] of max(0, margin - near) / margin, 0 without one, NaN as soon as one is NaN.  T lanes per candidate
+// stride the rows, all candidates in one pass (T G <= 256), then a fixed xor tree: the shape depends on (G, L) alone.
+template <class Near>
+__device__ __forceinline__ void tc_hinge_mean(const unsigned char* m, const int* scored, float* nearest, float* clearance, int G, int L,
+                                              float margin, Near near_of) {
+  const int tid = threadIdx.x;
+  int T = 64;
+  while (T > 1 && T * G > TC_THREADS) T >>= 1;
+  const int sub = tid & (T - 1), g = tid / T;
+  const bool act = g < G;
+  float sum = 0.f;
+  int ns = 0, nbad = 0;
+  if (act) {
+    const float inv = 1.f / margin;
+    for (int i = sub; i < L; i += T) {
+      const size_t r = (size_t)g * L + i;
+      float near = INFINITY;
+      if (!m[i]) near = near_of(g, i);
+      if (nearest) nearest[r] = near;
+      if (scored[i]) {
+        ++ns;
+        if (near != near) ++nbad;
+        else sum += fmaxf(0.f, margin - near) * inv;
+      }
+    }
+  }
+  for (int o = T >> 1; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, 64);
+    ns += __shfl_xor(ns, o, 64);
+    nbad += __shfl_xor(nbad, o, 64);
+  }
+  if (act && sub == 0) clearance[g] = nbad > 0 ? NAN : (ns > 0 ? sum / (float)ns : 0.f);
+}
+
 // row slots per lane and row groups per workgroup for R rows per scene
 static inline void tc_shape(long long R, int* rpt, int* nrg, int* row_tiles) {
   *rpt = R <= 256 ? 1 : (R <= 512 ? 2 : 4);
@@ -178,7 +273,7 @@ static inline size_t tc_ws_plane(int B, int G, int L, int n_points, int n_chunks
 // the workgroups of the partial launch (*blocks).  Returns A3D_OK or A3D_ERR_ARG with the message set.
 static inline int tc_scan_plan(const char* me, bool have_ptrs, const char* required, TrajScan* a, int* rpt, unsigned* blocks,
                                const unsigned char* tmask, const float* scene, const unsigned char* scene_mask, float* ws, int n_cam,
-                               int n_pix, float margin, int skip_head, int skip_tail, int n_chunks, int B, int G, int L) {
+                               int n_pix, float margin, int skip_head, int skip_tail, int n_chunks, int B, int G, int L, int K = 1) {
   if (!have_ptrs) { set_error("%s: null pointer (%s are required)", me, required); return A3D_ERR_ARG; }
   if (B <= 0 || G <= 0 || L <= 0) { set_error("%s: B, G and L must be positive (B=%d G=%d L=%d)", me, B, G, L); return A3D_ERR_ARG; }
   if (n_cam <= 0 || n_pix <= 0) { set_error("%s: n_cam and n_pix must be positive (n_cam=%d n_pix=%d)", me, n_cam, n_pix); return A3D_ERR_ARG; }
@@ -186,16 +281,20 @@ static inline int tc_scan_plan(const char* me, bool have_ptrs, const char* requi
   if (!(margin > 0.f && margin <= FLT_MAX)) { set_error("%s: margin must be finite and positive", me); return A3D_ERR_ARG; }
   if (skip_head < 0 || skip_tail < 0) { set_error("%s: negative skip (skip_head=%d skip_tail=%d)", me, skip_head, skip_tail); return A3D_ERR_ARG; }
   if (n_chunks < 0) { set_error("%s: n_chunks=%d is negative (0 = chosen by the entry)", me, n_chunks); return A3D_ERR_ARG; }
-  const long long N = (long long)n_cam * n_pix, R = (long long)G * L;
+  const long long N = (long long)n_cam * n_pix, R = (long long)G * K * L;
   if (N > 0x7fffffffLL) { set_error("%s: n_cam * n_pix overflows int (n_cam=%d n_pix=%d)", me, n_cam, n_pix); return A3D_ERR_ARG; }
-  if (R * 8 > 0x7fffffffLL) { set_error("%s: G * L * 8 overflows int (G=%d L=%d)", me, G, L); return A3D_ERR_ARG; }
+  if (R * 8 > 0x7fffffffLL) {
+    if (K == 1) set_error("%s: G * L * 8 overflows int (G=%d L=%d)", me, G, L);
+    else set_error("%s: G * K * L * 8 overflows int (G=%d K=%d L=%d)", me, G, K, L);
+    return A3D_ERR_ARG;
+  }
   if (B > 65535) { set_error("%s: B=%d exceeds 65535 scenes per call", me, B); return A3D_ERR_ARG; }
   a->tmask = tmask; a->scene = scene; a->smask = scene_mask; a->ws = ws;
   a->N = N; a->n_pix = n_pix;
-  a->n_chunks = tc_chunks(B, G, L, N, n_chunks);
+  a->n_chunks = tc_chunks(B, G * K, L, N, n_chunks);
   a->chunk_pts = (int)((N + a->n_chunks - 1) / a->n_chunks);
   tc_shape(R, rpt, &a->nrg, &a->row_tiles);
-  a->B = B; a->G = G; a->L = L;
+  a->B = B; a->G = G * K; a->L = L;
   const long long nb = (long long)a->n_chunks * a->row_tiles * B;
   if (nb > 0x7fffffffLL) { set_error("%s: %lld workgroups (n_chunks=%d) exceed the grid", me, nb, a->n_chunks); return A3D_ERR_ARG; }
   *blocks = (unsigned)nb;

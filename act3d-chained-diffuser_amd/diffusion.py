@@ -44,7 +44,8 @@ from .trajectory import (  # noqa: F401
     RANK_MAX_CANDIDATES, TrajectoryRanking, PlannerRanking, check_select, check_rot_weight, rank_trajectories, CLEARANCE_TERM,
     CLEARANCE_PRESET, TrajectoryClearance, SceneTrajectoryRanking, ScenePlannerRanking, check_scene_select, check_clearance_args,
     check_scene, prepare_scene, scan_workspace, check_trajectory_mask, trajectory_clearance, GUIDE_MAX_ROWS, GUIDE_KEYS, Guidance,
-    check_guide_args, check_guide, check_guide_shape, guided_segments, guide_trajectories, _number, _pose_rows, _mask_bytes, _guide_launch)
+    check_guide_args, check_guide, check_guide_shape, guided_segments, guide_trajectories, _number, _pose_rows, _mask_bytes, _guide_launch,
+    BODY_MAX_SPHERES, GripperBody, check_body, body_clearance)
 
 
 # ------------------------------------------------------------------------------------------------ DDPM tables
@@ -855,7 +856,8 @@ _SamplingCall = collections.namedtuple("_SamplingCall", ("G", "K", "guide", "w_c
 
 def check_sampling_call(B, Ln, D, T, pcd_obs, have_goal=True, *, num_samples=None, num_inference_steps=None, scheduler="ddpm", eta=0.0,
                         init_noise=None, step_noise=None, n_steps=None, select=None, rot_weight=1.0, scene_mask=None,
-                        clear_margin=0.05, clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True, pins=None):
+                        clear_margin=0.05, clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True, pins=None,
+                        clear_body=None):
     """Every host-side check of a sampling call (compute_trajectory, Actioner.predict), on shapes and Python values alone: nothing
     is launched, so a bad argument raises before any kernel runs.  B scenes of Ln steps and D = pose width + 2 signal channels; T:
     the chain length, or None where the caller leaves the schedule and the noise tables to the sampler (Actioner.predict, whose
@@ -885,6 +887,8 @@ def check_sampling_call(B, Ln, D, T, pcd_obs, have_goal=True, *, num_samples=Non
         check_solver_args(scheduler, eta, solver_order, lower_order_final)
     if pins is not None:
         check_pins(pins, B, D - 2)
+    if clear_body is not None:
+        check_body(clear_body)                              # whatever the rule weighs; nothing is copied to a device here
     guide = check_guide(guide)
     if guide is not None:
         check_guide_shape(G or 1, Ln, D)
@@ -1050,7 +1054,7 @@ class DiffusionPlanner(nn.Module):
                            init_noise=None, step_noise=None, visual_tokens=None, use_graph=False, n_steps=None,
                            return_trace=False, fused=None, num_inference_steps=None, scheduler="ddpm", eta=0.0, num_samples=None,
                            fused_conditioning=False, select=None, rot_weight=1.0, scene_mask=None, clear_margin=0.05,
-                           clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True, pins=None):
+                           clear_skip=(1, 1), guide=None, solver_order=2, lower_order_final=True, pins=None, clear_body=None):
         """Samples a trajectory batch.  By default the full chain of diffusion_timesteps ancestral DDPM steps, as the reference.
         num_inference_steps = K / scheduler / eta select a few-step sampler schedule instead (SamplerSchedule: K evenly strided
         timesteps, scheduler "ddpm" = strided ancestral sampling, "ddim" with 0 <= eta <= 1); step_noise is then (K, B, L, D) with row
@@ -1079,6 +1083,10 @@ class DiffusionPlanner(nn.Module):
         tensor in world coordinates, read in place (trajectory_clearance); scene_mask (B, C, H, W) drops points (the robot's own),
         clear_margin / clear_skip are its margin and skip.  self.last_ranking then also carries clearance (B, G) and nearest
         (B, G, L), before candidates.
+        clear_body: None or a gripper body (trajectory.check_body: sphere centres in the tool frame, radii, sweep).  With a rule that
+        weighs "clearance" the term and last_ranking.nearest then come from body_clearance: the spheres turn with every waypoint and
+        are swept along the segments between waypoints.  With any other rule the body is checked and otherwise ignored.  No preset
+        body ships (body_clearance says why).  `guide` keeps pushing the tool point.  None (default): today's launches and bits.
         guide: clearance guidance WHILE the trajectory is drawn (guide_trajectories, a3d_traj_guide).  A number is the push; a dict
         maps "push" (default 1.0), "smooth" (0.0) and "start" (0.5, in [0, 1)) to numbers.  With n executed steps, the step at
         position i >= floor(start n) is followed by one guide step on the signal it produced (the terminal step always is), on
@@ -1108,7 +1116,7 @@ class DiffusionPlanner(nn.Module):
                                    num_inference_steps=num_inference_steps, scheduler=scheduler, eta=eta, init_noise=init_noise,
                                    step_noise=step_noise, n_steps=n_steps, select=select, rot_weight=rot_weight, scene_mask=scene_mask,
                                    clear_margin=clear_margin, clear_skip=clear_skip, guide=guide, solver_order=solver_order,
-                                   lower_order_final=lower_order_final, pins=pins)
+                                   lower_order_final=lower_order_final, pins=pins, clear_body=clear_body)
         # ---- the plan: which launches serve the call, from the shapes and the CU count alone
         multi = head.attn_rounds * head.feat_scales > 1
         plan = sampler_plan(B_scene, call.G, Ln, D, head.curr_gripper_embed.weight.shape[1], head.num_attn_heads, self.n_steps,
@@ -1129,7 +1137,7 @@ class DiffusionPlanner(nn.Module):
         run = lambda x: self._run_steps(x, plan, tb if sched is None else sched, call, c, state, gd, segments, trace)
         traj = self._replay(key, run, c.traj, static, state) if replay else run(c.traj)
         return self._finish(call, c, traj, trace, gd, segments, replay, trajectory_mask, pcd_obs, goal_gripper, select, rot_weight,
-                            scene_mask, clear_margin, clear_skip)
+                            scene_mask, clear_margin, clear_skip, clear_body)
 
     def _condition(self, plan, sched, G, trajectory_mask, rgb_obs, pcd_obs, instruction, curr_gripper, goal_gripper, init_noise,
                    step_noise, visual_tokens, fused_conditioning, pins=None):
@@ -1331,7 +1339,7 @@ class DiffusionPlanner(nn.Module):
         return x
 
     def _finish(self, call, c, traj, trace, gd, segments, replay, trajectory_mask, pcd_obs, goal_gripper, select, rot_weight,
-                scene_mask, clear_margin, clear_skip):
+                scene_mask, clear_margin, clear_skip, clear_body=None):
         """last_guidance, poses, the candidate axis, ranking (last_ranking) -> compute_trajectory's result.  trajectory_mask,
         pcd_obs (the caller's tensor, in world coordinates) and goal_gripper are the call's own, per scene."""
         G, Ln = call.G, traj.shape[1]
@@ -1349,7 +1357,7 @@ class DiffusionPlanner(nn.Module):
                 trace = [x.reshape(c.B_scene, G, Ln, x.shape[-1]) for x in trace]
         if select is not None:
             rk = rank_trajectories(final, trajectory_mask, goal_gripper, self.gripper_loc_bounds, select, rot_weight, scene=pcd_obs,
-                                   scene_mask=scene_mask, margin=clear_margin, skip=clear_skip)
+                                   scene_mask=scene_mask, margin=clear_margin, skip=clear_skip, body=clear_body)
             self.last_ranking = (ScenePlannerRanking if len(rk) == 7 else PlannerRanking)(*rk, candidates=final)
             final = rk.selected
         return final if trace is None else (final, trace)

@@ -135,6 +135,8 @@ LR_DECAY_KINDS = {k[len("A3D_LR_"):].lower(): v for k, v in _DEFINES.items() if 
 
 # pins per scene of one a3d_traj_pins call
 TRAJ_PINS_MAX = _DEFINES["A3D_TRAJ_PINS_MAX"]
+# spheres of one a3d_traj_body_clearance body
+TRAJ_BODY_MAX_SPHERES = _DEFINES["A3D_TRAJ_BODY_MAX_SPHERES"]
 
 _lib = None
 

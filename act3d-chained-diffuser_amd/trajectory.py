@@ -1,5 +1,6 @@
 """What happens to the sampler's trajectory candidates besides the denoising itself: pinned waypoints (traj_pins, a3d_traj_pins),
-ranking and selection (rank_trajectories, a3d_traj_rank), scene clearance (trajectory_clearance, a3d_traj_clearance) and clearance
+ranking and selection (rank_trajectories, a3d_traj_rank), scene clearance (trajectory_clearance, a3d_traj_clearance; with a gripper
+body of swept spheres body_clearance, a3d_traj_body_clearance) and clearance
 guidance (guide_trajectories, a3d_traj_guide), with their named tuples and the host-side checks of their arguments.  The reference
 has none of these (Actioner.predict, online_evaluation/utils_with_rlbench.py:120-230, executes the one trajectory it samples).
 diffusion.py (the planner, compute_trajectory's keywords) re-exports every name of this module."""
@@ -346,6 +347,99 @@ def trajectory_clearance(trajectories, trajectory_mask, scene, scene_mask=None, 
     return TrajectoryClearance(nearest, clearance)
 
 
+# ------------------------------------------------------------------------------------------------ body-aware swept clearance
+BODY_MAX_SPHERES = O.L.TRAJ_BODY_MAX_SPHERES        # spheres of one body (a3d_traj_body_clearance)
+# a gripper body: sphere centres in the TOOL frame (K, 3) and radii (K,), in metres; sweep: score the segment to the next waypoint.
+# No preset ships: where the fingers and the palm lie in the tool frame depends on the robot and on the frame convention of the data.
+GripperBody = collections.namedtuple("GripperBody", ("offsets", "radii", "sweep"), defaults=(True,))
+
+
+def check_body(body, device=None):
+    """Validates a gripper body and returns GripperBody(offsets (K, 3) fp32, radii (K,) fp32, sweep bool), the tensors on `device`
+    (None: where they are).  body: a GripperBody or a dict with "offsets", "radii" and optionally "sweep" (default True); offsets
+    and radii are tensors or nested sequences of numbers.  ValueError for wrong ranks or shapes, K outside 1 .. 8, a sweep that is not
+    a bool (or 0 / 1), non-finite offsets, negative or non-finite radii.  The values are checked where the tensors live on the
+    host; tensors already on a device are NOT copied back for it (no synchronisation): a non-finite offset then gives NaN rows, a
+    NaN radius a NaN `nearest`, in the kernel."""
+    if isinstance(body, dict):
+        bad = [k for k in body if k not in GripperBody._fields]
+        if bad or "offsets" not in body or "radii" not in body:
+            raise ValueError("body: a dict with the keys 'offsets', 'radii' and optionally 'sweep', got %s" % sorted(body))
+        offsets, radii, sweep = body["offsets"], body["radii"], body.get("sweep", True)
+    elif isinstance(body, tuple) and all(hasattr(body, k) for k in GripperBody._fields):
+        offsets, radii, sweep = body.offsets, body.radii, body.sweep
+    else:
+        raise ValueError("body must be a GripperBody or a dict with offsets, radii and sweep, got %s" % type(body).__name__)
+    if isinstance(sweep, bool) or (isinstance(sweep, int) and sweep in (0, 1)):
+        sweep = bool(sweep)
+    else:
+        raise ValueError("body: sweep must be a bool, got %r" % (sweep,))
+    try:
+        offsets = offsets.detach() if torch.is_tensor(offsets) else torch.as_tensor(offsets, dtype=torch.float32)
+        radii = radii.detach() if torch.is_tensor(radii) else torch.as_tensor(radii, dtype=torch.float32)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError("body: offsets and radii must be tensors or nested sequences of numbers (%s)" % e) from None
+    if offsets.dim() != 2 or offsets.shape[1] != 3:
+        raise ValueError("body: offsets must be (K, 3) sphere centres in the tool frame, got %s" % (tuple(offsets.shape),))
+    K = offsets.shape[0]
+    if not 1 <= K <= BODY_MAX_SPHERES:
+        raise ValueError("body: K = %d spheres, a body has 1 to %d" % (K, BODY_MAX_SPHERES))
+    if tuple(radii.shape) != (K,):
+        raise ValueError("body: radii must be (K,) = (%d,), got %s" % (K, tuple(radii.shape)))
+    for name, x in (("offsets", offsets), ("radii", radii)):
+        if not (x.is_floating_point() or x.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)):
+            raise ValueError("body: %s must hold numbers, got %s" % (name, x.dtype))
+    if not offsets.is_cuda and not bool(torch.isfinite(offsets.float()).all()):
+        raise ValueError("body: offsets must be finite")
+    if not radii.is_cuda and not bool((torch.isfinite(radii.float()) & (radii.float() >= 0)).all()):
+        raise ValueError("body: radii must be finite and >= 0")
+    offsets = O._c(offsets.to(device=device, dtype=torch.float32))
+    radii = O._c(radii.to(device=device, dtype=torch.float32))
+    return GripperBody(offsets, radii, sweep)
+
+
+def body_clearance(trajectories, trajectory_mask, scene, body, scene_mask=None, margin=0.05, skip=(1, 1)):
+    """trajectory_clearance for a gripper BODY instead of the tool point, in THREE launches (a3d_traj_body_clearance,
+    csrc/traj_body.hip): K <= 8 spheres in the tool frame, rotated with every waypoint's quaternion (the matrix pose_to_signal
+    emits, completed by its third column), each swept along the straight segment of its centre to the next valid waypoint.
+    trajectories, trajectory_mask, scene, scene_mask, margin, skip: the arguments of trajectory_clearance, except that the
+    quaternion (w, x, y, z) of a pose row is read as well.  body: check_body.
+    With j the rank of a valid row among the n valid rows of its scene, the end row of row j is the row of rank j + 1 when
+    body.sweep is set and j + 1 < n - skip[1], else the row itself: gaps of the mask are stepped over, the approach to the goal row
+    is not swept with the default skip (contact is intended there), the last scored row is a degenerate segment.  Sphere k of row j
+    moves from a = p_j + R(q_j) o_k to c = p_e + R(q_e) o_k on a straight line (a capsule; the rotation is not interpolated inside
+    a segment).  Returns TrajectoryClearance(nearest (B, G, L), clearance (B, G)): nearest = min_k (distance of the segment to the
+    nearest counted point - r_k), SIGNED (negative: a sphere contains a scene point), +inf without a counted point and on padded
+    rows, NaN where a sphere centre of the row or of its end row is not finite (a zero quaternion included); clearance = the mean
+    over the scored rows of max(0, margin - nearest) / margin, NOT clamped above (in [0, 1 + max r / margin]: penetration costs
+    more than touching), 0 without a scored row, NaN as soon as a scored row is NaN.  offsets and radii are read by the kernels at
+    launch time: a captured call replayed after they were changed in place sees the new values (give device tensors to a call that
+    is captured: host values are copied to the device first).  With one sphere of radius 0 at the
+    tool point and sweep=False this is trajectory_clearance, bit for bit.  Bit-identical from run to run.
+    No preset body ships: sphere positions in the tool frame depend on the robot and on the data's frame convention, and neither
+    has been verified here.  A worked example with MADE-UP numbers (a palm sphere and two finger-tip spheres of a parallel gripper
+    whose fingers point along the tool frame's +z and open along its y):
+        body = GripperBody(offsets=[[0.0, 0.0, -0.06], [0.0, 0.04, 0.0], [0.0, -0.04, 0.0]], radii=[0.04, 0.015, 0.015])"""
+    B, G, Ln, Dp = _check_candidates(trajectories, trajectory_mask)
+    sc = prepare_scene(scene, scene_mask, B)
+    mg, sh, st = check_clearance_args(margin, skip)
+    body = check_body(body)
+    O.L.require_gpu(trajectories, trajectory_mask, scene, scene_mask)
+    P = O._c(trajectories.detach().float())
+    body = check_body(body, P.device)                        # already on the device: nothing is copied, nothing is read back
+    K = body.offsets.shape[0]
+    tm = _mask_bytes(trajectory_mask)
+    dev = P.device
+    nearest = torch.empty((B, G, Ln), device=dev, dtype=torch.float32)
+    clearance = torch.empty((B, G), device=dev, dtype=torch.float32)
+    n = O.L.load().a3d_traj_body_clearance_ws_floats(B, G, Ln, K, sc.n_cam * sc.n_pix, 0)
+    ws = torch.empty((n,), device=dev, dtype=torch.float32)
+    O.L.call("a3d_traj_body_clearance", P.data_ptr(), tm.data_ptr(), body.offsets.data_ptr(), body.radii.data_ptr(), K,
+             1 if body.sweep else 0, sc.cloud.data_ptr(), None if sc.mask is None else sc.mask.data_ptr(), sc.n_cam, sc.n_pix, mg, sh, st,
+             nearest.data_ptr(), clearance.data_ptr(), ws.data_ptr(), 0, B, G, Ln, Dp, O.L.stream())
+    return TrajectoryClearance(nearest, clearance)
+
+
 # ------------------------------------------------------------------------------------------------ clearance guidance
 GUIDE_MAX_ROWS = 256                    # a3d_traj_guide: one thread per row of a trajectory
 GUIDE_KEYS = ("push", "smooth", "start")
@@ -459,7 +553,7 @@ def guide_trajectories(signals, trajectory_mask, scene, bounds, *, scene_mask=No
 
 
 def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, select="consensus", rot_weight=1.0, scene=None,
-                      scene_mask=None, margin=0.05, skip=(1, 1)):
+                      scene_mask=None, margin=0.05, skip=(1, 1), body=None):
     """Ranks the G candidate trajectories of every scene and selects one, in ONE launch (a3d_traj_rank, csrc/traj_rank.hip); nothing
     is copied to the host.  trajectories: (B, G, L, Dp) fp32 poses [xyz | quaternion | opening], Dp = 7 or 8, scene-major as
     compute_trajectory(num_samples=G) returns them, G <= 64; trajectory_mask: (B, L), non-zero = padded row (any pattern); goal:
@@ -474,7 +568,9 @@ def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, sel
     preset "clear") needs `scene`; the score is then the five-term sum plus w_clearance * clearance, added last, the call runs
     trajectory_clearance's two launches before the ranking launch (a3d_traj_rank_extra, the same kernel) and returns
     SceneTrajectoryRanking: the five fields above in order, then clearance (B, G) and nearest (B, G, L).  A rule that does not weigh
-    the term runs the one launch above and returns TrajectoryRanking, whatever `scene` is."""
+    the term runs the one launch above and returns TrajectoryRanking, whatever `scene` is.
+    body: None or a gripper body (check_body).  With a rule that weighs "clearance" the term and `nearest` then come from
+    body_clearance (three launches instead of two); with any other rule the body is checked and otherwise ignored, as `scene` is."""
     B, G, Ln, Dp = _check_candidates(trajectories, trajectory_mask)
     if goal is not None and (not torch.is_tensor(goal) or goal.dim() != 2 or goal.shape[0] != B or goal.shape[1] < 7):
         raise ValueError("goal must be (B, >= 7) pose rows with B = %d, got %s" % (
@@ -485,6 +581,8 @@ def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, sel
             raise ValueError("bounds must be (2, 3), got %s" % (tuple(bounds.shape),))
     w, wc = check_scene_select(select, goal is not None, bounds is not None, scene is not None)
     rw = check_rot_weight(rot_weight)
+    if body is not None:
+        body = check_body(body)
     if wc != 0.0:
         check_scene(scene, scene_mask, B)
         check_clearance_args(margin, skip)
@@ -502,7 +600,8 @@ def rank_trajectories(trajectories, trajectory_mask, goal=None, bounds=None, sel
             w[0], w[1], w[2], w[3], w[4], rw, best.data_ptr(), order.data_ptr(), scores.data_ptr(), terms.data_ptr(), selected.data_ptr(),
             B, G, Ln, Dp)
     if wc != 0.0:
-        cl = trajectory_clearance(P, tm, scene, scene_mask, margin, skip)
+        cl = trajectory_clearance(P, tm, scene, scene_mask, margin, skip) if body is None else \
+            body_clearance(P, tm, scene, body, scene_mask, margin, skip)
         O.L.call("a3d_traj_rank_extra", *args, cl.clearance.data_ptr(), wc, O.L.stream())
         return SceneTrajectoryRanking(best, order, scores, terms, selected, cl.clearance, cl.nearest)
     O.L.call("a3d_traj_rank", *args, O.L.stream())

@@ -589,6 +589,33 @@ size_t a3d_traj_clearance_ws_floats(int B, int G, int L, int n_points, int n_chu
 int a3d_traj_clearance(const float* poses, const unsigned char* tmask, const float* scene, const unsigned char* scene_mask, int n_cam,
                        int n_pix, float margin, int skip_head, int skip_tail, float* nearest, float* clearance, float* ws,
                        int n_chunks, int B, int G, int L, int Dp, void* stream);
+/* Body-aware swept clearance: a3d_traj_clearance for a gripper body of K spheres instead of the tool point, in three launches
+ * (csrc/traj_body.hip).  None in the reference.  poses, tmask, scene, scene_mask, n_cam, n_pix, margin, skip_head, skip_tail, "counted
+ * point", "scored row", n_chunks: as a3d_traj_clearance, but the quaternion (w, x, y, z) of a pose row is read too.  offsets: device
+ * [K][3], sphere centres in the tool frame (metres); radii: device [K], finite and >= 0; 1 <= K <= A3D_TRAJ_BODY_MAX_SPHERES;
+ * sweep: 0 or 1.  Both are read at launch time by the kernels, never by the host.
+ *   R(q)              q divided by max(|q|, 1e-10), t = 2 / |q^|^2; the first two columns as a3d_pose_to_signal emits them, the
+ *                     third [t (xz + yw), t (yz - xw), 1 - t (xx + yy)].  A zero quaternion gives a non-finite R: a NaN row.
+ *   end row e(j)      of the valid row of rank j among the scene's n valid rows: the row of rank j + 1 when sweep is set and
+ *                     j + 1 < n - skip_tail, else the row itself (gaps of the mask are stepped over; the approach to a skipped
+ *                     tail is not swept; the last scored row is a degenerate segment)
+ *   sphere k of row j a = p_j + R(q_j) o_k, c = p_e + R(q_e) o_k, d = c - a, inv = 1 / |d|^2 (0 when |d|^2 == 0); per counted point s:
+ *                     u = s - a, t = clamp(fmaf(u_z, d_z, fmaf(u_y, d_y, u_x d_x)) inv, 0, 1), w = fmaf(-t, d, u),
+ *                     d^2 = fmaf(w_z, w_z, fmaf(w_y, w_y, w_x w_x)), not contracted; dist_k = sqrt(min d^2), one root per row and sphere
+ *   nearest[b][g][i]  min_k (dist_k - r_k), signed (negative: a sphere contains a counted point); +inf without a counted point and
+ *                     for padded rows (not computed); NaN where a or c of any sphere is not finite.  May be NULL.
+ *   clearance[b][g]   mean over the scored rows of max(0, margin - nearest) / margin, not clamped above: in [0, 1 + max r / margin];
+ *                     0 without a scored row; NaN as soon as a scored row's nearest is NaN.
+ * With K = 1, o = 0, r = 0, sweep = 0 and finite non-zero quaternions both outputs have the bits of a3d_traj_clearance.
+ * ws: a3d_traj_body_clearance_ws_floats(B, G, L, K, N, n_chunks) floats owned by the caller (partial minima [n_chunks][B][G][K][L],
+ * segment records [B][G][K][L][8] and 3 B L ints).  The minimum is exact: bit-identical from run to run and for every n_chunks; no
+ * atomics.  Stream-ordered, no host synchronisation, capturable.  G <= 64 candidates (G K row groups may exceed 64); B <= 65535. */
+#define A3D_TRAJ_BODY_MAX_SPHERES 8
+size_t a3d_traj_body_clearance_ws_floats(int B, int G, int L, int K, int n_points, int n_chunks);
+int a3d_traj_body_clearance(const float* poses, const unsigned char* tmask, const float* offsets, const float* radii, int K, int sweep,
+                            const float* scene, const unsigned char* scene_mask, int n_cam, int n_pix, float margin, int skip_head,
+                            int skip_tail, float* nearest, float* clearance, float* ws, int n_chunks, int B, int G, int L, int Dp,
+                            void* stream);
 /* One clearance-guidance step on trajectory SIGNALS, in place, in two launches (csrc/traj_guide.hip).  None in the reference.
  * traj: [B][G][L][D] fp32 signals, scene-major, D = 9 or 10; only channels 0..2 (positions normalised to bounds) are read or
  * written.  tmask, scene, scene_mask, n_cam, n_pix, margin, skip_head, skip_tail, "counted point" and d^2: as a3d_traj_clearance.
