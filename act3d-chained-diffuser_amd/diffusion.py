@@ -541,40 +541,25 @@ class DiffusionHead(nn.Module):
         H = self.num_attn_heads
         dev = ctx.device
         Sp = O.ceil_to(S, 64)
-        f4 = 4
         freq = O.rope_freq(E, dev)
         silu = F.silu(time_sin)                                         # (T, E)
         st = {"S": S, "Sp": Sp, "layers": [], "tensors": [], "freq": freq, "sem": self._sem(Ln, E, dev), "kmask": kmask, "n_cand": n_cand}
         ctx = O._c(ctx)
         xyz = O._c(ctx_xyz.float())
         for lay in self._cross_layers():
-            mha = lay.cross_12
-            # the split-fp16 operand formats (csrc/denoise.hip header): K rows16, V planes16 with the ones channel -- projection, RoPE
-            # and formatting in ONE launch per layer (rounds 2 - 5: a [B S, 2E] fp32 projection in HBM + two formatting passes)
-            Kf = torch.empty((B, H, Sp, 32), device=dev, dtype=torch.float16)
-            Vt = torch.empty((B, H, 2, 16, Sp), device=dev, dtype=torch.float16)
-            wk, bk = mha.in_proj_weight.data_ptr() + E * E * f4, mha.in_proj_bias.data_ptr() + E * f4
-            if O._fused_proj(E):
-                O.L.call("a3d_proj_rope_split16", ctx.data_ptr(), E, wk, E, bk, E, xyz.data_ptr(), 1.0, Kf.data_ptr(), None, 2,
-                         None, 1.0, None, Vt.data_ptr(), 2 | 4, freq.data_ptr(), B, S, Sp, E, H, O.L.stream())
-            else:
-                # E = 30 / 90 (E % 4 != 0): the fused writer reads rows of X and W as float4 and refuses them; the rule of the op-by-op
-                # path (ops.write_operands): one linear launch for k | v, then one formatting launch per operand
-                kv = O.linear_raw(ctx.data_ptr(), E, wk, E, bk, B * S, 2 * E, E, dev)
-                O.L.call("a3d_rope_split16", kv.data_ptr(), 2 * E, xyz.data_ptr(), freq.data_ptr(), 1.0, Kf.data_ptr(), None, 2,
-                         B, S, Sp, E, H, O.L.stream())
-                O.L.call("a3d_rope_split16", kv.data_ptr() + E * f4, 2 * E, None, freq.data_ptr(), 1.0, None, Vt.data_ptr(), 2 | 4,
-                         B, S, Sp, E, H, O.L.stream())
+            # the split-fp16 operand formats (csrc/denoise.hip header): K rows16, V planes16 with the ones channel, in ONE launch per
+            # layer (E % 4 != 0 -- E = 30 / 90 -- which the fused writer's float4 reads refuse: one linear launch, two formatting ones)
+            Kf, Vt = O.ctx_kv_cache16(ctx, xyz, lay.cross_12, H)
             mods = [O.linear2d(silu, a.modulation[1].weight, a.modulation[1].bias) for a in (lay.adaln_12, lay.adaln_1, lay.adaln_ff1)]
             st["layers"].append({"lay": lay, "Kf": Kf, "Vt": Vt, "mods": mods})
             st["tensors"] += [Kf, Vt] + mods
         st["lang_kv"] = None
         if self.use_instruction:
             mha = self.traj_lang_attention[0].layers[0].cross_12
+            ip = O.InProj(mha.in_proj_weight, mha.in_proj_bias, E)
             instr = O._c(instr)
             st["S_lang"] = instr.shape[1]
-            st["lang_kv"] = O.linear_raw(instr.data_ptr(), E, mha.in_proj_weight.data_ptr() + E * E * f4, E,
-                                         mha.in_proj_bias.data_ptr() + E * f4, B * instr.shape[1], 2 * E, E, dev)
+            st["lang_kv"] = O.linear_raw(instr.data_ptr(), E, ip.wk, E, ip.bk, B * instr.shape[1], 2 * E, E, dev)
             st["tensors"].append(st["lang_kv"])
         st["nsplit"] = max(1, min(8, Sp // 128, -(-DN_TARGET_WGS // (B * H))))
         nws = O.L.load().a3d_dn_cross_ws_floats(B, H, st["nsplit"])

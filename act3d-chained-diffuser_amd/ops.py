@@ -25,6 +25,14 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _or_empty(device, *ts):          # optional tensors (xyz, key mask) for save_for_backward: empty for None, a flag in ctx.meta says so
+    return tuple(torch.empty(0, device=device) if t is None else t for t in ts)
+
+
+def _or_none(present, *ts):
+    return ts if present else (None,) * len(ts)
+
+
 def grad_buf(p):
     """The tensor wgrad kernels accumulate into for parameter ``p`` (created zeroed on first use)."""
     if p.grad is None:
@@ -342,8 +350,33 @@ Slot = collections.namedtuple("Slot", "rows planes word", defaults=(None,) * 3) 
 
 def group_layout(w0, roles, E):
     """-> (byte offset of the group's rows in in_proj_weight, in in_proj_bias, byte offset of each role's column slice in the group's
-    fp32 rows, their leading dimension in floats).  The one place the pointer arithmetic of the packed projection is done."""
+    fp32 rows, their leading dimension in floats).  With InProj, the one place the pointer arithmetic of the packed projection is done."""
     return w0 * E * E * 4, w0 * E * 4, tuple(i * E * 4 for i in range(len(roles))), len(roles) * E
+
+
+class InProj:
+    """Addresses inside one packed fp32 projection (in_proj_weight [3E][E], in_proj_bias [3E]), built once per Function call and plain
+    ints from then on (the eager per-launch path).  wq / wk / wv, bq / bk / bv: device pointers of a role's weight rows and bias (block
+    i of group_layout); grad: the same addressing of the parameters' gradient buffers, which are created when it is first asked for."""
+    __slots__ = ("weight", "bias", "E", "wq", "wk", "wv", "bq", "bk", "bv", "_grad")
+
+    def __init__(self, weight, bias, E):
+        wp, bp = weight.data_ptr(), bias.data_ptr()
+        self.weight, self.bias, self.E, self._grad = weight, bias, E, None
+        self.wq, self.wk, self.wv = wp, wp + E * E * 4, wp + 2 * E * E * 4
+        self.bq, self.bk, self.bv = bp, bp + E * 4, bp + 2 * E * 4
+
+    @property
+    def grad(self):
+        if self._grad is None:
+            self._grad = InProj(grad_buf(self.weight), grad_buf(self.bias), self.E)
+        return self._grad
+
+    def group(self, w0, roles):                   # group_layout: the byte offsets are from wq / bq, and the same in grad
+        return group_layout(w0, roles, self.E)
+
+    def rows(self, w0, roles):                    # the group's rows as a slice, for the callers that need tensor VIEWS (weight[rows])
+        return slice(w0 * self.E, (w0 + len(roles)) * self.E)
 
 
 def alloc_operands(f16, roles, B, H, Lqp, Sp, device, need_bwd):
@@ -586,14 +619,9 @@ def ctx_kv_operands16(value, value_xyz, mhas, H):
     xyz = None if value_xyz is None else _c(value_xyz.to(F32))
     pairs = [(torch.empty((B, H, Sp, 32), device=dev, dtype=torch.float16), torch.empty((B, H, Sp, 32), device=dev, dtype=torch.float16))
              for _ in mhas]
-    f4 = 4
-    args = []
-    for j in range(CTX_KV_MAX_LAYERS):
-        if j < len(mhas):
-            w, b = mhas[j].in_proj_weight, mhas[j].in_proj_bias
-            args += [w.data_ptr() + E * E * f4, b.data_ptr() + E * f4, pairs[j][0].data_ptr(), pairs[j][1].data_ptr()]
-        else:
-            args += [None, None, None, None]
+    ips = [InProj(m.in_proj_weight, m.in_proj_bias, E) for m in mhas]
+    args = [a for ip, (Kr, Vr) in zip(ips, pairs) for a in (ip.wk, ip.bk, Kr.data_ptr(), Vr.data_ptr())]
+    args += [None] * 4 * (CTX_KV_MAX_LAYERS - len(mhas))
     L.call("a3d_ctx_kv_proj16", value.data_ptr(), E, None if xyz is None else xyz.data_ptr(), *args, E, freq.data_ptr(), len(mhas),
            B, S, Sp, E, H, 0, L.stream())
     return pairs
@@ -916,10 +944,7 @@ class AttnBlockFn(torch.autograd.Function):
                                nograd=not need_bwd)
         Y = linear2d(O.view(B * Lq, E), out_w, out_b, drop=drop, site=site + 1)   # seq1 + dropout(attn_out): Y is the dropped branch
         y, mean, rstd = add_layernorm(resid.view(B * Lq, E), Y, ln_g, ln_b)
-        ctx.save_for_backward(q_in, k_in, v_in, resid, Y, mean, rstd, Qs, Ks, Vt, O, LSE,
-                              q_xyz if q_xyz is not None else torch.empty(0, device=dev),
-                              k_xyz if k_xyz is not None else torch.empty(0, device=dev),
-                              kmask if kmask is not None else torch.empty(0, device=dev))
+        ctx.save_for_backward(q_in, k_in, v_in, resid, Y, mean, rstd, Qs, Ks, Vt, O, LSE, *_or_empty(dev, q_xyz, k_xyz, kmask))
         ctx.params = (in_w, in_b, out_w, out_b, ln_g, ln_b)
         ctx.extra = extra
         ctx.need_bwd = need_bwd
@@ -943,10 +968,7 @@ class AttnBlockFn(torch.autograd.Function):
             raise RuntimeError("AttnBlockFn.backward: the forward ran with grad_mode=False (a gradient-free pass: adaptive low part "
                                "of P, no backward operand formats); call it through ops.attn_block or pass "
                                "grad_mode=torch.is_grad_enabled()")
-        if not has_xyz:
-            q_xyz = k_xyz = None
-        if not has_mask:
-            kmask = None
+        (q_xyz, k_xyz), (kmask,) = _or_none(has_xyz, q_xyz, k_xyz), _or_none(has_mask, kmask)
         freq = rope_freq(E, dev)
         dy = _c(dy).view(B * Lq, E)
         if ctx.drop is None:
@@ -957,14 +979,15 @@ class AttnBlockFn(torch.autograd.Function):
         wgrad2d(dYo, O.view(B * Lq, E), out_w, out_b)
         dQp, dK, dV = attn_core_bwd(Qs, Ks, Vt, kmask, O, dO.view(B, Lq, E), LSE, B, H, Lq, Lqp, S, Sp, nsplit,
                                     extra=ctx.extra, drop=ctx.drop, site=ctx.site)
-        gW, gb = grad_buf(in_w), grad_buf(in_b)
+        ip = InProj(in_w, in_b, E)
+        g = ip.grad
         st = L.stream()
         needs = ctx.needs_input_grad
         fold_q = ctx.q_is_resid and needs[3]                     # d_q_in is added into dS (no reader of dS / dYo is left by then)
         x, d_in = (q_in, k_in, v_in), [None, None, None]
         role = {"q": Role(q_xyz, scale, Lq, Lqp, dQp, nsplit), "k": Role(k_xyz, 1.0, S, Sp, dK), "v": Role(None, 1.0, S, Sp, dV)}
         for src, w0, roles in PROJ_GROUPS[mode]:
-            w_off, b_off, cols, ld = group_layout(w0, roles, E)
+            w_off, b_off, cols, ld = ip.group(w0, roles)
             N = role[roles[0]].n
             to = _group_grad_route(roles, needs, ctx.sink is not None, fold_q)
             if to == "parked":
@@ -972,16 +995,16 @@ class AttnBlockFn(torch.autograd.Function):
                 # GEMMs of all blocks that read this context run once, at the gate
                 ptr, ldg = ctx.sink.park(x[src], ld)
             else:
-                g = torch.empty((B * N, ld), device=dev, dtype=F32)
-                ptr, ldg = g.data_ptr(), ld
+                rows = torch.empty((B * N, ld), device=dev, dtype=F32)
+                ptr, ldg = rows.data_ptr(), ld
             for r, c in zip(roles, cols):
                 ro = role[r]
                 rope_merge(ro.grad, ro.nsplit, ro.xyz, freq, ro.scale, ptr + c, ldg, B, ro.n, ro.npad, E, H)
             if to == "parked":
-                blocks = slice(w0 * E, (w0 + len(roles)) * E)
-                d_in[src] = ctx.sink.parked_done(in_w[blocks], gW[blocks], gb[blocks])
+                blocks = ip.rows(w0, roles)
+                d_in[src] = ctx.sink.parked_done(in_w[blocks], g.weight[blocks], g.bias[blocks])
                 continue
-            wgrad_raw(ptr, ld, x[src].data_ptr(), E, gW.data_ptr() + w_off, E, gb.data_ptr() + b_off, B * N, ld, E, dev, st)
+            wgrad_raw(ptr, ld, x[src].data_ptr(), E, g.wq + w_off, E, g.bq + b_off, B * N, ld, E, dev, st)
             if to is None:
                 continue
             if to == "sink":
@@ -989,7 +1012,7 @@ class AttnBlockFn(torch.autograd.Function):
                 out = buf.view(B * N, E)
             else:
                 out, acc = (dS, True) if to == "fold" else (None, False)
-            d = linear_raw(ptr, ld, in_w.data_ptr() + w_off, E, None, B * N, E, ld, dev, act=3 if acc else 0, transposed=True, out=out)
+            d = linear_raw(ptr, ld, ip.wq + w_off, E, None, B * N, E, ld, dev, act=3 if acc else 0, transposed=True, out=out)
             if to == "sink":
                 d_in[src] = ctx.sink.end()                       # None: the sink's gate node hands the total to autograd
             elif to == "fresh":
@@ -1009,6 +1032,38 @@ def sq_nsplit(B, S):
     return max(1, min((S + 63) // 64, SQ_TARGET_WGS // B))
 
 
+def sq_keys_fwd(kv_in, k_xyz, ip, qrot, freq, H, project_v, st):
+    """The key-streaming pass of both single-query Functions (a3d_sq_attn_fwd) over the context kv_in [B][S][E] -> (xbar [B][H][E],
+    lse [B][H], o, nsplit).  project_v: the value projection is applied inside and o [B][E] is the attention output
+    (SingleQueryAttnBlockFn); else o is None and a3d_qs_post_fwd projects xbar (QueryLayerFn).  ip: the layer's InProj."""
+    B, S, E = kv_in.shape
+    nsplit = sq_nsplit(B, S)
+    new = lambda *shape: torch.empty(shape, device=kv_in.device, dtype=F32)
+    ws, xbar, lse, o = new(L.load().a3d_sq_fwd_ws_floats(B, H, E, nsplit)), new(B, H, E), new(B, H), new(B, E) if project_v else None
+    wv, bv = (ip.wv, ip.bv) if project_v else (None, None)
+    L.call("a3d_sq_attn_fwd", kv_in.data_ptr(), L.nz(k_xyz), ip.wk, E, ip.bk, wv, E, bv, qrot.data_ptr(), freq.data_ptr(), ws.data_ptr(),
+           xbar.data_ptr(), lse.data_ptr(), L.nz(o), B, S, E, H, nsplit, st)
+    return xbar, lse, o, nsplit
+
+
+def sq_bwd_ws(B, H, E, nsplit, device):       # the workspace of sq_keys_bwd: dxbar [B][H][E] | cD [B][H] | weight-gradient partials
+    return torch.empty((L.load().a3d_sq_bwd_ws_floats(B, H, E, nsplit),), device=device, dtype=F32)
+
+
+def sq_keys_bwd(kv_in, k_xyz, ip, qrot, freq, xbar, lse, dO, ws, dX, acc, H, nsplit, st):
+    """Backward of sq_keys_fwd -> dqp [nsplit][B][H][1][16], the rotated-query gradient partials; dWk / dbk are accumulated.  dO: the
+    gradient of o (the value projection's gradients are accumulated too); None: the value projection is the caller's, whose
+    a3d_qs_post_bwd has left dxbar | cD at the head of ws.  dX [B][S][E] is written (acc None: a3d_sq_attn_bwd; False) or added to."""
+    B, S, E = kv_in.shape
+    g = ip.grad
+    dqp = torch.empty((nsplit, B, H, 1, 16), device=kv_in.device, dtype=F32)
+    wv, dwv, dbv = (None, None, None) if dO is None else (ip.wv, g.wv, g.bv)
+    L.call("a3d_sq_attn_bwd" if acc is None else "a3d_sq_attn_bwd_acc", kv_in.data_ptr(), L.nz(k_xyz), ip.wk, E, ip.bk, wv, E,
+           qrot.data_ptr(), freq.data_ptr(), xbar.data_ptr(), lse.data_ptr(), L.nz(dO), ws.data_ptr(), dX.data_ptr(), dqp.data_ptr(),
+           g.wk, E, g.bk, dwv, E, dbv, B, S, E, H, nsplit, *(() if acc is None else (int(acc),)), st)
+    return dqp
+
+
 class SingleQueryAttnBlockFn(torch.autograd.Function):
     """y = LayerNorm(resid + out_proj(MHA(q, ctx, ctx))) for ONE query per sample (Act3D's query stream, act3d.py:467-480)
     on csrc/single_query.hip: the value projection commutes with the weighted sum for a single query, the key projection
@@ -1021,29 +1076,18 @@ class SingleQueryAttnBlockFn(torch.autograd.Function):
         B, _, E = q_in.shape
         S = kv_in.shape[1]
         dev = q_in.device
-        f4 = 4
         if q_xyz is not None:
             q_xyz, k_xyz = _c(q_xyz.to(F32)), _c(k_xyz.to(F32))
         freq = rope_freq(E, dev)
         scale = float(E // H) ** -0.5
-        wp, bp = in_w.data_ptr(), in_b.data_ptr()
-        q_pre = linear_raw(q_in.data_ptr(), E, wp, E, bp, B, E, E, dev)
+        ip = InProj(in_w, in_b, E)
+        q_pre = linear_raw(q_in.data_ptr(), E, ip.wq, E, ip.bq, B, E, E, dev)
         qrot = torch.empty((B, H, 1, 16), device=dev, dtype=F32)
         L.call("a3d_rope_rows_f32", q_pre.data_ptr(), E, L.nz(q_xyz), freq.data_ptr(), scale, qrot.data_ptr(), B, 1, 1, E, H, L.stream())
-        nsplit = sq_nsplit(B, S)
-        lib = L.load()
-        ws = torch.empty((lib.a3d_sq_fwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)
-        xbar = torch.empty((B, H, E), device=dev, dtype=F32)
-        lse = torch.empty((B, H), device=dev, dtype=F32)
-        o = torch.empty((B, E), device=dev, dtype=F32)
-        L.call("a3d_sq_attn_fwd", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, wp + 2 * E * E * f4, E,
-               bp + 2 * E * f4, qrot.data_ptr(), freq.data_ptr(), ws.data_ptr(), xbar.data_ptr(), lse.data_ptr(), o.data_ptr(), B, S, E,
-               H, nsplit, L.stream())
+        xbar, lse, o, nsplit = sq_keys_fwd(kv_in, k_xyz, ip, qrot, freq, H, True, L.stream())
         Y = linear2d(o, out_w, out_b)
         y, mean, rstd = add_layernorm(resid.view(B, E), Y, ln_g, ln_b)
-        ctx.save_for_backward(q_in, kv_in, resid, Y, mean, rstd, qrot, xbar, lse, o,
-                              q_xyz if q_xyz is not None else torch.empty(0, device=dev),
-                              k_xyz if k_xyz is not None else torch.empty(0, device=dev))
+        ctx.save_for_backward(q_in, kv_in, resid, Y, mean, rstd, qrot, xbar, lse, o, *_or_empty(dev, q_xyz, k_xyz))
         ctx.params = (in_w, in_b, out_w, out_b, ln_g, ln_b)
         ctx.meta = (B, S, E, H, scale, nsplit, q_xyz is not None)
         return y.view(B, 1, E)
@@ -1054,27 +1098,20 @@ class SingleQueryAttnBlockFn(torch.autograd.Function):
         in_w, in_b, out_w, out_b, ln_g, ln_b = ctx.params
         B, S, E, H, scale, nsplit, has_xyz = ctx.meta
         dev = dy.device
-        f4 = 4
-        if not has_xyz:
-            q_xyz = k_xyz = None
+        q_xyz, k_xyz = _or_none(has_xyz, q_xyz, k_xyz)
         freq = rope_freq(E, dev)
         dS = add_layernorm_bwd(resid.view(B, E), Y, ln_g, ln_b, mean, rstd, _c(dy).view(B, E))
         dO = dgrad2d(dS, out_w)
         wgrad2d(dS, o, out_w, out_b)
-        gW, gb = grad_buf(in_w), grad_buf(in_b)
-        wp, bp = in_w.data_ptr(), in_b.data_ptr()
-        lib = L.load()
-        ws = torch.empty((lib.a3d_sq_bwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)
+        ip = InProj(in_w, in_b, E)
+        g = ip.grad
+        ws = sq_bwd_ws(B, H, E, nsplit, dev)
         dX = torch.empty((B, S, E), device=dev, dtype=F32)
-        dqp = torch.empty((nsplit, B, H, 1, 16), device=dev, dtype=F32)
-        L.call("a3d_sq_attn_bwd", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, wp + 2 * E * E * f4, E, qrot.data_ptr(),
-               freq.data_ptr(), xbar.data_ptr(), lse.data_ptr(), dO.data_ptr(), ws.data_ptr(), dX.data_ptr(), dqp.data_ptr(),
-               gW.data_ptr() + E * E * f4, E, gb.data_ptr() + E * f4, gW.data_ptr() + 2 * E * E * f4, E, gb.data_ptr() + 2 * E * f4,
-               B, S, E, H, nsplit, L.stream())
+        dqp = sq_keys_bwd(kv_in, k_xyz, ip, qrot, freq, xbar, lse, dO, ws, dX, None, H, nsplit, L.stream())
         dq_pre = torch.empty((B, E), device=dev, dtype=F32)
         rope_merge(dqp, nsplit, q_xyz, freq, scale, dq_pre.data_ptr(), E, B, 1, 1, E, H)
-        wgrad_raw(dq_pre.data_ptr(), E, q_in.data_ptr(), E, gW.data_ptr(), E, gb.data_ptr(), B, E, E, dev)
-        d_q_in = dgrad2d(dq_pre, in_w[:E]).view(B, 1, E) if ctx.needs_input_grad[0] else None
+        wgrad_raw(dq_pre.data_ptr(), E, q_in.data_ptr(), E, g.wq, E, g.bq, B, E, E, dev)
+        d_q_in = dgrad2d(dq_pre, in_w[ip.rows(0, "q")]).view(B, 1, E) if ctx.needs_input_grad[0] else None
         return (d_q_in, dX if ctx.needs_input_grad[1] else None, dS.view(B, 1, E) if ctx.needs_input_grad[2] else None) + (None,) * 9
 
 
@@ -1095,40 +1132,29 @@ class QueryLayerFn(torch.autograd.Function):
         B, _, E = x.shape
         S = kv_in.shape[1]
         dev = x.device
-        f4 = 4
         if q_xyz is not None:
             q_xyz, k_xyz = _c(q_xyz.to(F32)), _c(k_xyz.to(F32))
         freq = rope_freq(E, dev)
         scale = float(E // H) ** -0.5
-        wp, bp = in_w.data_ptr(), in_b.data_ptr()
+        ip = InProj(in_w, in_b, E)
         st = L.stream()
-        lib = L.load()
         qrot = torch.empty((B, H, 1, 16), device=dev, dtype=F32)
-        L.call("a3d_qs_pre_fwd", x.data_ptr(), wp, bp, L.nz(q_xyz), freq.data_ptr(), scale, qrot.data_ptr(), B, E, H, st)
-        nsplit = sq_nsplit(B, S)
-        ws = torch.empty((lib.a3d_sq_fwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)
-        xbar = torch.empty((B, H, E), device=dev, dtype=F32)
-        lse = torch.empty((B, H), device=dev, dtype=F32)
-        L.call("a3d_sq_attn_fwd", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, None, E, None, qrot.data_ptr(),
-               freq.data_ptr(), ws.data_ptr(), xbar.data_ptr(), lse.data_ptr(), None, B, S, E, H, nsplit, st)
-        save = torch.empty((lib.a3d_qs_save_floats(B, E),), device=dev, dtype=F32)
+        L.call("a3d_qs_pre_fwd", x.data_ptr(), ip.wq, ip.bq, L.nz(q_xyz), freq.data_ptr(), scale, qrot.data_ptr(), B, E, H, st)
+        xbar, lse, _, nsplit = sq_keys_fwd(kv_in, k_xyz, ip, qrot, freq, H, False, st)
+        save = torch.empty((L.load().a3d_qs_save_floats(B, E),), device=dev, dtype=F32)
         y = torch.empty((B, 1, E), device=dev, dtype=F32)
-        qp = QueryLayerFn._params(in_w, in_b, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2, E)
+        qp = QueryLayerFn._params(ip, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2)
         L.call("a3d_qs_post_fwd", xbar.data_ptr(), x.data_ptr(), L.byref(qp), save.data_ptr(), y.data_ptr(), B, E, H, st)
-        ctx.save_for_backward(x, kv_in, qrot, xbar, lse, save,
-                              q_xyz if q_xyz is not None else torch.empty(0, device=dev),
-                              k_xyz if k_xyz is not None else torch.empty(0, device=dev))
+        ctx.save_for_backward(x, kv_in, qrot, xbar, lse, save, *_or_empty(dev, q_xyz, k_xyz))
         ctx.params = (in_w, in_b, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2)
         ctx.meta = (B, S, E, H, scale, nsplit, q_xyz is not None)
         ctx.sink = sink if (sink is not None and ctx.needs_input_grad[1] and tuple(kv_in.shape) == sink.shape) else None
         return y
 
     @staticmethod
-    def _params(in_w, in_b, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2, E):
-        f4 = 4
-        return L.QsParams(wv=in_w.data_ptr() + 2 * E * E * f4, bv=in_b.data_ptr() + 2 * E * f4, wo=out_w.data_ptr(), bo=out_b.data_ptr(),
-                          g1=g1.data_ptr(), b1=b1.data_ptr(), w1=w1.data_ptr(), c1=c1.data_ptr(), w2=w2.data_ptr(), c2=c2.data_ptr(),
-                          g2=g2.data_ptr(), b2=b2.data_ptr())
+    def _params(ip, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2):
+        return L.QsParams(wv=ip.wv, bv=ip.bv, wo=out_w.data_ptr(), bo=out_b.data_ptr(), g1=g1.data_ptr(), b1=b1.data_ptr(),
+                          w1=w1.data_ptr(), c1=c1.data_ptr(), w2=w2.data_ptr(), c2=c2.data_ptr(), g2=g2.data_ptr(), b2=b2.data_ptr())
 
     @staticmethod
     def backward(ctx, dy):
@@ -1136,33 +1162,26 @@ class QueryLayerFn(torch.autograd.Function):
         in_w, in_b, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2 = ctx.params
         B, S, E, H, scale, nsplit, has_xyz = ctx.meta
         dev = dy.device
-        f4 = 4
-        if not has_xyz:
-            q_xyz = k_xyz = None
+        q_xyz, k_xyz = _or_none(has_xyz, q_xyz, k_xyz)
         freq = rope_freq(E, dev)
         st = L.stream()
-        lib = L.load()
-        gW, gb = grad_buf(in_w), grad_buf(in_b)
-        wp, bp = in_w.data_ptr(), in_b.data_ptr()
-        qp = QueryLayerFn._params(in_w, in_b, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2, E)
-        gr = L.QsGrads(dwv=gW.data_ptr() + 2 * E * E * f4, dbv=gb.data_ptr() + 2 * E * f4, dwo=grad_buf(out_w).data_ptr(),
-                       dbo=grad_buf(out_b).data_ptr(), dg1=grad_buf(g1).data_ptr(), db1=grad_buf(b1).data_ptr(),
-                       dw1=grad_buf(w1).data_ptr(), dc1=grad_buf(c1).data_ptr(), dw2=grad_buf(w2).data_ptr(), dc2=grad_buf(c2).data_ptr(),
-                       dg2=grad_buf(g2).data_ptr(), db2=grad_buf(b2).data_ptr())
-        ws = torch.empty((lib.a3d_sq_bwd_ws_floats(B, H, E, nsplit),), device=dev, dtype=F32)    # dxbar | cD | weight-gradient partials
+        ip = InProj(in_w, in_b, E)
+        g = ip.grad
+        qp = QueryLayerFn._params(ip, out_w, out_b, g1, b1, w1, c1, w2, c2, g2, b2)
+        gr = L.QsGrads(dwv=g.wv, dbv=g.bv, dwo=grad_buf(out_w).data_ptr(), dbo=grad_buf(out_b).data_ptr(), dg1=grad_buf(g1).data_ptr(),
+                       db1=grad_buf(b1).data_ptr(), dw1=grad_buf(w1).data_ptr(), dc1=grad_buf(c1).data_ptr(), dw2=grad_buf(w2).data_ptr(),
+                       dc2=grad_buf(c2).data_ptr(), dg2=grad_buf(g2).data_ptr(), db2=grad_buf(b2).data_ptr())
+        ws = sq_bwd_ws(B, H, E, nsplit, dev)                 # a3d_qs_post_bwd leaves dxbar | cD at its head for the key pass
         dx = torch.empty((B, 1, E), device=dev, dtype=F32)
         L.call("a3d_qs_post_bwd", _c(dy).data_ptr(), x.data_ptr(), xbar.data_ptr(), save.data_ptr(), L.byref(qp), L.byref(gr),
-               ws.data_ptr(), ws.data_ptr() + B * H * E * f4, dx.data_ptr(), B, E, H, st)
-        dqp = torch.empty((nsplit, B, H, 1, 16), device=dev, dtype=F32)
+               ws.data_ptr(), ws.data_ptr() + B * H * E * 4, dx.data_ptr(), B, E, H, st)
         if ctx.sink is not None:
             dXb, acc = ctx.sink.begin()                      # the context's shared gradient buffer: written or summed into
         else:
             dXb, acc = torch.empty((B, S, E), device=dev, dtype=F32), False
-        L.call("a3d_sq_attn_bwd_acc", kv_in.data_ptr(), L.nz(k_xyz), wp + E * E * f4, E, bp + E * f4, None, E, qrot.data_ptr(),
-               freq.data_ptr(), xbar.data_ptr(), lse.data_ptr(), None, ws.data_ptr(), dXb.data_ptr(), dqp.data_ptr(),
-               gW.data_ptr() + E * E * f4, E, gb.data_ptr() + E * f4, None, E, None, B, S, E, H, nsplit, 1 if acc else 0, st)
+        dqp = sq_keys_bwd(kv_in, k_xyz, ip, qrot, freq, xbar, lse, None, ws, dXb, acc, H, nsplit, st)
         dX = ctx.sink.end() if ctx.sink is not None else dXb
-        L.call("a3d_qs_pre_bwd", dqp.data_ptr(), nsplit, L.nz(q_xyz), freq.data_ptr(), scale, x.data_ptr(), wp, gW.data_ptr(), gb.data_ptr(),
+        L.call("a3d_qs_pre_bwd", dqp.data_ptr(), nsplit, L.nz(q_xyz), freq.data_ptr(), scale, x.data_ptr(), ip.wq, g.wq, g.bq,
                dx.data_ptr(), B, E, H, st)
         return (dx if ctx.needs_input_grad[0] else None, dX if ctx.needs_input_grad[1] else None) + (None,) * 16
 
@@ -1827,6 +1846,20 @@ def kv_cache_build(k_in, k_xyz, mha, H):
                                           mha.in_proj_bias.data_ptr(), None, k_xyz, B, S, S, E, H, k_in.device, False,
                                           fused=_fused_proj(E))
     return {"Ks": Ks, "Vt": Vt, "S": S, "Sp": Sp}
+
+
+def ctx_kv_cache16(ctx, xyz, mha, H):
+    """Step-invariant context operands of one cross-attention layer of the fused sampler (csrc/denoise.hip) -> (Kf [B][H][Sp][32] fp16
+    hi | lo rows, rotated by xyz; Vt [B][H][2][16][Sp] fp16 hi / lo planes with the ones channel): the (k, v) group of mode "kv" through
+    write_operands.  dn_cross reads K rows + V planes whatever the training side uses, so neither _rows_only() nor ATTN_MODE is asked."""
+    ctx, xyz = _c(ctx), _c(xyz.to(F32))
+    B, S, E = ctx.shape
+    Sp, dev = ceil_to(S, 64), ctx.device
+    Kf, Vt = (torch.empty(shape, device=dev, dtype=torch.float16) for shape in ((B, H, Sp, 32), (B, H, 2, 16, Sp)))
+    write_operands(True, PROJ_GROUPS["kv"][1:], {"k": Role(xyz, 1.0, S, Sp), "v": Role(None, 1.0, S, Sp)},
+                   {"k": Slot(Kf, None, PLANE_PARTS), "v": Slot(None, Vt, V_PLANES)}, rope_freq(E, dev), B, E, H, dev, (None, ctx, ctx),
+                   mha.in_proj_weight.data_ptr(), mha.in_proj_bias.data_ptr(), fused=_fused_proj(E))
+    return Kf, Vt
 
 
 @torch.no_grad()
